@@ -11,14 +11,18 @@ step is the node's own mining loop — `miner/service.MiningService.step`, the c
   -> broadcast the 96-byte work packet from rank 0.
 
 The DAG is built sharded over the ranks and all-gathered before timing (reported as
-dag_build_s). After timing, rank 0 re-hashes up to 8 of the gathered shares with the host
-golden model (light mode, `_core.kawpow_hash`) and exits non-zero on any mismatch.
+dag_build_s). A plain run does no more than that: set up, warm up, time the K steps, print the
+line. `--dump-outputs DIR` also writes what the last timed step handed the leader (the gathered
+shares and hash counters) as DIR/*.npy, the same from run to run with the same arguments.
 
-Extras on the same line: Equihash(200,9) Sol/s (config 3) and batch header verification of
-the committed 10k-header fixture through models/verify.process_headers, PoW + DGW/contextual,
-every header required to be accepted (config 5; per-epoch setup excluded, reported).
+`--full` adds, after the timed steps: rank 0 re-hashes up to 8 of the gathered shares with the
+host golden model (light mode, `_core.kawpow_hash`) and exits non-zero on any mismatch; and, as
+extras on the same line: the GPU's clocks around the timed steps, Equihash(200,9) Sol/s (config 3)
+and batch header verification of the committed 10k-header fixture through
+models/verify.process_headers, PoW + DGW/contextual, every header required to be accepted
+(config 5; per-epoch setup excluded, reported).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     (N>1 either way: bench.py starts its N ranks itself, one child process per GPU, or
      python -m torch.distributed.run --nnodes=1 --nproc-per-node N \\
           --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...;
@@ -247,6 +251,33 @@ def _equihash_bench(args, hdr, height: int, rank: int, log) -> dict:
             "shares_checked": checked}
 
 
+def _dump_outputs(out_dir: str, records) -> None:
+    """--dump-outputs: what the last timed MiningService.step handed the leader on rank 0, i.e. every
+    rank's gathered record of the window it took in that step. One row per share, ordered by
+    (rank, nonce), every array float64 (all values are 32-bit words or small counts, so exact):
+
+      share_rank.npy    (n,)    the rank that found the share
+      share_nonce.npy   (n, 2)  the 64-bit nonce as (high, low) 32-bit words
+      share_mix.npy     (n, 8)  mix hash, little-endian 32-bit words in storage order
+      share_final.npy   (n, 8)  final hash, the same
+      rank_hashes.npy   (ranks,) nonces hashed by each rank's window
+
+    The job, the nonce windows and so the arrays are the same from run to run with the same arguments."""
+    import numpy as np
+
+    from nodexa_chain_core_amd.miner.service import _as_record
+
+    recs = [_as_record(r) for r in records]
+    rows = sorted((r, s.nonce, s.mix_hash, s.final_hash) for r, rec in enumerate(recs) for s in rec.shares)
+    words = lambda col: np.array([np.frombuffer(row[col], dtype="<u4") for row in rows],  # noqa: E731
+                                 dtype=np.float64).reshape(len(rows), 8)
+    nonce = np.array([(row[1] >> 32, row[1] & 0xFFFFFFFF) for row in rows], dtype=np.float64).reshape(len(rows), 2)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in (("share_rank", [row[0] for row in rows]), ("share_nonce", nonce), ("share_mix", words(2)),
+                      ("share_final", words(3)), ("rank_hashes", [rec.hashes for rec in recs])):
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(arr, dtype=np.float64))
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -263,9 +294,16 @@ def main() -> int:
     ap.add_argument("--verify", type=int, default=1, help="1: time BASELINE config 5 (batch header verify)")
     ap.add_argument("--check-shares", type=int, default=8, help="shares re-hashed on the host after timing")
     ap.add_argument("--corrupt-dag", action="store_true",
-                    help="test hook: damage every 64th DAG item after the build; the share check must fail")
+                    help="test hook: damage every 64th DAG item after the build; the share check of --full must fail")
     ap.add_argument("--device", choices=("gpu", "cpu"), default="gpu",
                     help="cpu: rehearse the same loop and collectives on host devices over gloo (tests)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also: the host re-hash of --check-shares shares, the Equihash loop "
+                         "(--equihash), batch header verify (--verify) and the GPU's clocks around the timed steps; "
+                         "a plain run only sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step handed the leader (every rank's shares and hash "
+                         "counter) as DIR/<name>.npy, float64")
     ap.add_argument("--quiet", action="store_true")
     args = ap.parse_args()
 
@@ -283,10 +321,15 @@ def main() -> int:
     from nodexa_chain_core_amd import _build
 
     cpu = args.device == "cpu"
-    if cpu:
-        _build.build_core()
-    else:
-        _build.build_all()
+    try:
+        if cpu:
+            _build.build_core()
+        else:
+            _build.build_all()
+    except PermissionError as e:
+        # a tree built by someone else that this user may not write to (no build lock, nothing to
+        # rebuild into): run what is built; the imports and kernel loads below fail if a piece is missing
+        print(f"bench.py: not rebuilding ({e}); using the tree as built", file=sys.stderr)
     from nodexa_chain_core_amd import _core
     from nodexa_chain_core_amd.chain.header import BlockHeader
     from nodexa_chain_core_amd.miner.search import CpuSearchDevice, Work
@@ -340,11 +383,19 @@ def main() -> int:
             sync()
         del ep
 
-    leader = BenchLeader(work) if rank == 0 else None
+    class RecordingLeader(BenchLeader):  # --dump-outputs: also keeps the records of the latest step
+        last: list = []
+
+        def on_results(self, records) -> None:
+            self.last = records
+            super().on_results(records)
+
+    leader = (RecordingLeader if args.dump_outputs else BenchLeader)(work) if rank == 0 else None
     svc = MiningService(dev, leader, window=max(block, args.batch // block * block))
     batch = svc.window
 
-    gpu_start = gpu_snapshot(world)  # before the warmup: amdsmi's first call is slow, keep it out of the loop
+    # before the warmup: amdsmi's first call is slow, keep it out of the loop
+    gpu_start = gpu_snapshot(world) if args.full else {}
     svc.step()  # the work packet goes out (the loop starts idle)
     for _ in range(args.warmup):
         svc.step()
@@ -359,7 +410,8 @@ def main() -> int:
     sync()
     W.barrier()
     elapsed = W.all_reduce_max(time.perf_counter() - t_start)
-    gpu_end = gpu_snapshot(world)
+    gpu_end = gpu_snapshot(world) if args.full else {}
+    last_records = leader.last if leader is not None and args.dump_outputs else None  # of the last timed step
     total = batch * ws * args.steps
     mhs = total / elapsed / 1e6
     # the same windows on the device clock: window ends 2..K of the timed steps (K - 2 windows; the
@@ -373,17 +425,19 @@ def main() -> int:
     while svc.step():
         pass
     svc.pipe.drain()
+    if last_records is not None:
+        _dump_outputs(args.dump_outputs, last_records)
 
     checked = bad = 0
-    if rank == 0:
+    if rank == 0 and args.full:
         # full host re-hash (light mode) of the gathered shares: mix and final must both match
         t0 = time.time()
         for s in leader.shares[:args.check_shares]:
             checked += 1
             bad += not s.verify_full(height, work.header_hash, work.boundary, ctx=ctx)
         log(f"[bench] {checked} shares re-hashed on the host in {time.time() - t0:.1f}s: {bad} mismatches")
-    bad = W.all_reduce_sum_int(bad)
-    if args.check_shares and W.all_reduce_sum_int(checked) == 0:
+    bad = W.all_reduce_sum_int(bad) if args.full else 0
+    if args.full and args.check_shares and W.all_reduce_sum_int(checked) == 0:
         raise SystemExit("no shares to re-hash: the search produced none")
     if bad:
         raise SystemExit(f"{bad} GPU shares failed the full host re-hash")
@@ -394,10 +448,10 @@ def main() -> int:
         torch.cuda.empty_cache()
 
     eq = None
-    if args.equihash and not cpu:
+    if args.full and args.equihash and not cpu:
         eq = _equihash_bench(args, hdr, height, rank, log)
 
-    verify = _verify_headers_bench(log) if args.verify and not cpu else None
+    verify = _verify_headers_bench(log) if args.full and args.verify and not cpu else None
     if verify is not None:
         # the same pipeline at the headline epoch (BASELINE config 5 on a live chain's heights)
         v384 = _verify_headers_bench(log, VERIFY_FIXTURE_E384)
@@ -420,6 +474,7 @@ def main() -> int:
             "vs_baseline": round(mhs / base, 3) if base else None,
             "dtype": "u32",
             "device": args.device,
+            "full": args.full,  # false: the extras below (clocks, share re-hash, Equihash, header verify) were not run
             "data": "synthetic regtest header + sequential nonces; the real epoch DAG generated on the GPU "
                     "(no chain data)",
             "config": {

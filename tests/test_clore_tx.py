@@ -1,7 +1,7 @@
-"""clore-tx against the reference's own util test vectors (test/util/data/clore-util-test.json,
-read in place from the reference checkout: every case's arguments, stdin, expected hex / JSON output
-and exit code). The vectors carry Bitcoin-style addresses and keys, so they run with the 0 / 5 / 128
-version bytes they were generated with."""
+"""clore-tx against the reference's own util test vectors (its test/util/data: every clore-tx case of
+clore-util-test.json with its arguments, stdin, expected hex / JSON output and exit code, packed into
+tests/golden/clore_tx_vectors.json, one case per line). The vectors carry Bitcoin-style addresses and
+keys, so they run with the 0 / 5 / 128 version bytes they were generated with."""
 import io
 import json
 import os
@@ -10,30 +10,26 @@ import pytest
 
 from nodexa_chain_core_amd.cli import clore_tx
 
-DATA = "/root/reference/test/util/data"
+VECTORS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "clore_tx_vectors.json")
 PREFIXES = ["-pubkeyprefix=0", "-scriptprefix=5", "-secretprefix=128"]
 
 
 def _cases():
-    path = os.path.join(DATA, "clore-util-test.json")
-    if not os.path.exists(path):
-        return []
-    return [c for c in json.load(open(path)) if c.get("exec", "").endswith("clore-tx")]
+    with open(VECTORS) as f:
+        return json.load(f)
 
 
-@pytest.mark.skipif(not _cases(), reason="reference util vectors not present")
 @pytest.mark.parametrize("case", _cases(), ids=lambda c: " ".join(c["args"])[:60])
 def test_util_vector(case, capsys):
     args = list(case["args"])
     flags = [a for a in args if a.startswith("-") and a != "-"]
     rest = [a for a in args if not (a.startswith("-") and a != "-")]
-    stdin = io.StringIO(open(os.path.join(DATA, case["input"])).read()) if "input" in case else None
+    stdin = io.StringIO(case["input_text"]) if "input" in case else None
     out = io.StringIO()
     rc = clore_tx.main(PREFIXES + flags + rest, stdin=stdin, stdout=out)
     assert rc == case.get("return_code", 0), capsys.readouterr().err
     if "output_cmp" in case:
-        want = open(os.path.join(DATA, case["output_cmp"])).read()
         if case["output_cmp"].endswith(".json"):
-            assert json.loads(out.getvalue()) == json.loads(want)
+            assert json.loads(out.getvalue()) == case["output"]
         else:
-            assert out.getvalue().strip() == want.strip()
+            assert out.getvalue().strip() == case["output"]

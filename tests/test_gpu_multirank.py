@@ -37,7 +37,7 @@ def test_two_rank_bench_on_one_gpu(gpu, launcher):
         pre += ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                 "--master-addr", "127.0.0.1", "--master-port", str(_free_port())]
     cmd = pre + ["bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", str(1 << 23),
-                 "--equihash", "2", "--verify", "1", "--check-shares", "4"]
+                 "--equihash", "2", "--verify", "1", "--check-shares", "4", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]

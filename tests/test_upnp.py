@@ -177,7 +177,7 @@ def test_node_upnp_flag(core, tmp_path, igd):
     try:
         c = RPCClient("127.0.0.1", n.rpc.port, "u", "p")
         assert _wait(lambda: any(x["address"] == EXTERNAL_IP for x in c.getnetworkinfo()["localaddresses"]))
-        assert n.upnp.mapped >= 1
+        assert _wait(lambda: n.upnp.mapped >= 1)  # the mapper advertises the address before it adds the mapping
     finally:
         n.stop()
     assert igd.actions[-1][0] == "DeletePortMapping"
