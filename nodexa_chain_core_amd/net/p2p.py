@@ -7,7 +7,10 @@ handling of PeerLogicValidation::ProcessMessage (src/net_processing.cpp:1527)
 for version / verack / ping / pong / getheaders / headers / inv / getdata / block /
 sendheaders. Headers-first sync follows src/net_processing.cpp:1369-1500:
 `getheaders` with a block locator, <= 2000 headers per reply, a follow-up
-`getheaders` while replies are full, then `getdata` for the block bodies.
+`getheaders` while replies are full; the block bodies are then asked for by the tracked
+downloader (net/blockfetch.py), a window at a time and from every peer that has them.
+Connection slots, the inbound eviction selection and the time limits are in net/peerman.py;
+a `p2p-maint` thread runs ConnectionManager.maintain() once a second for everything timed.
 
 The MI355X difference is where a `headers` batch goes: instead of the reference's
 serial CheckBlockHeader per header under cs_main (src/validation.cpp:12017-12035),
@@ -33,16 +36,19 @@ from ..utils import log, sync
 from ..utils.metrics import REGISTRY
 from . import protocol as P
 from .addrman import AddrMan, load_banlist, save_banlist
+from .blockfetch import EXTRA_PEER_CHECK_INTERVAL, MINIMUM_CONNECT_TIME, STALE_CHECK_INTERVAL, BlockFetcher
 from .bloom import MAX_SCRIPT_ELEMENT_SIZE, BloomFilter, merkle_block
 from .compact import (CompactBlock, blocktxn_payload, getblocktxn_payload, parse_blocktxn, parse_getblocktxn)
 from .netbase import ProxyTable
+from .peerman import (DEFAULT_MAX_PEER_CONNECTIONS, HANDSHAKE_TIMEOUT, PING_INTERVAL, TIMEOUT_INTERVAL,
+                      EvictionCandidate, NetGroupKeyer, connection_slots, select_node_to_evict)
 from .timedata import TimeData
 
 _core = core()
 DEFAULT_MISBEHAVING_BANTIME = 60 * 60 * 24  # -bantime (src/net.h)
 MSG_FILTERED_BLOCK, MSG_CMPCT_BLOCK = 3, 4
 MAX_ADDR_TO_SEND = 1000
-DEFAULT_MAX_OUTBOUND = 8  # MAX_OUTBOUND_CONNECTIONS
+DEFAULT_MAX_OUTBOUND = 8  # MAX_OUTBOUND_CONNECTIONS (the reference's is 12, see PARITY.md)
 
 
 def _ser_addr(entries) -> bytes:
@@ -92,21 +98,57 @@ class Peer:
         self.cmpct_hb = False                    # high-bandwidth mode: push cmpctblock unasked
         self.partial: dict[bytes, tuple] = {}    # block hash -> (CompactBlock, slots) awaiting blocktxn
         self.getaddr_answered = False
-        self.connected_at = time.time()
+        self.manual = False  # -connect / -addnode: exempt from the outbound eviction rules
+        self.connected_at = mgr.clock()
         self.last_recv = self.last_send = 0.0
+        self.last_block_time = self.last_tx_time = 0.0  # a block / tx of this peer's accepted as new
+        self.keyed_net_group = mgr.net_group_key(addr[0])
+        # keep-alive (nPingNonceSent, nPingUsecStart, nPingUsecTime, nMinPingUsecTime, fPingQueued)
+        self.ping_nonce = 0
+        self.ping_start = 0.0
+        self.ping_time: float | None = None
+        self.min_ping = float("inf")
+        self.ping_queued = False
         self._send_lock = threading.Lock()
         self.closed = threading.Event()
         self.thread = threading.Thread(target=self._run, name=f"p2p-peer{self.id}", daemon=True)
+
+    def _sent(self, cmd: str, n: int) -> None:
+        self.bytes_sent += n
+        self.mgr.total_sent += n
+        self.mgr.record_sent(n)
+        self.last_send = self.mgr.clock()
+        REGISTRY.inc("p2p_bytes_sent_total", n, command=cmd)
 
     def send(self, cmd: str, payload: bytes = b"") -> None:
         msg = P.frame(self.mgr.magic, cmd, payload)
         with self._send_lock:
             self.sock.sendall(msg)
-        self.bytes_sent += len(msg)
-        self.mgr.total_sent += len(msg)
-        self.mgr.record_sent(len(msg))
-        self.last_send = time.time()
-        REGISTRY.inc("p2p_bytes_sent_total", len(msg), command=cmd)
+        self._sent(cmd, len(msg))
+
+    def try_send(self, cmd: str, payload: bytes = b"") -> bool:
+        """Send without waiting for this peer: False (and nothing written) if another thread is
+        in the middle of a send to it or its socket buffer is full; a buffer that takes only part
+        of the frame closes the peer. For threads that serve every peer (maintenance, block
+        requests made on another peer's thread), which one slow peer must not hold up."""
+        msg = P.frame(self.mgr.magic, cmd, payload)
+        if not self._send_lock.acquire(blocking=False):
+            return False
+        try:
+            try:
+                n = self.sock.send(msg, socket.MSG_DONTWAIT)
+            except (BlockingIOError, InterruptedError):
+                return False
+            if n < len(msg):
+                # half a frame is out and the rest would have to wait for this peer: the stream
+                # cannot be kept in step without waiting, so the peer goes
+                log.log_print("net", f"peer {self.id}: send buffer full in the middle of a frame, disconnecting")
+                self.close()
+                return False
+        finally:
+            self._send_lock.release()
+        self._sent(cmd, len(msg))
+        return True
 
     def send_version(self) -> None:
         self.sent_version = True
@@ -146,7 +188,7 @@ class Peer:
                 cmd, payload = P.read_message(self.sock, self.mgr.magic)
                 self.bytes_recv += P.HEADER_SIZE + len(payload)
                 self.mgr.total_recv += P.HEADER_SIZE + len(payload)
-                self.last_recv = time.time()
+                self.last_recv = self.mgr.clock()
                 REGISTRY.inc("p2p_bytes_recv_total", P.HEADER_SIZE + len(payload), command=cmd)
                 if self.mgr.drop_messages_test and random.randrange(self.mgr.drop_messages_test) == 0:
                     # -dropmessagestest=<n> (src/net_processing.cpp:1530)
@@ -166,13 +208,23 @@ class Peer:
 
     def as_dict(self) -> dict:
         host, port = self.addr[:2]
-        return {"id": self.id, "addr": f"{host}:{port}", "inbound": self.inbound, "version": self.info.get("version", 0),
-                "subver": self.info.get("user_agent", ""), "startingheight": self.info.get("start_height", -1),
-                "bytessent": self.bytes_sent, "bytesrecv": self.bytes_recv, "conntime": int(self.connected_at),
-                "lastsend": int(self.last_send), "lastrecv": int(self.last_recv), "banscore": self.misbehavior,
-                "synced_headers": self.mgr.state.height(), "relaytxes": self.info.get("relay", True),
-                "services": "%016x" % self.info.get("services", 0), "whitelisted": self.whitelisted,
-                "timeoffset": self.info.get("timeoffset", 0)}
+        fetch = self.mgr.fetcher.peer_view(self.id)
+        d = {"id": self.id, "addr": f"{host}:{port}", "inbound": self.inbound, "version": self.info.get("version", 0),
+             "subver": self.info.get("user_agent", ""), "startingheight": self.info.get("start_height", -1),
+             "bytessent": self.bytes_sent, "bytesrecv": self.bytes_recv, "conntime": int(self.connected_at),
+             "lastsend": int(self.last_send), "lastrecv": int(self.last_recv), "banscore": self.misbehavior,
+             "synced_headers": fetch["synced_headers"], "synced_blocks": fetch["synced_blocks"],
+             "inflight": fetch["inflight"], "relaytxes": self.info.get("relay", True),
+             "services": "%016x" % self.info.get("services", 0), "whitelisted": self.whitelisted,
+             "timeoffset": self.info.get("timeoffset", 0)}
+        # seconds, as the reference prints them; pingwait only while a ping is outstanding
+        if self.ping_time is not None:
+            d["pingtime"] = self.ping_time
+        if self.min_ping != float("inf"):
+            d["minping"] = self.min_ping
+        if self.ping_nonce:
+            d["pingwait"] = max(0.0, self.mgr.clock() - self.ping_start)
+        return d
 
 
 class ConnectionManager:
@@ -180,8 +232,10 @@ class ConnectionManager:
 
     def __init__(self, state, params, gpus: list[int] | None = None, listen: tuple[str, int] | None = None,
                  verify_mode: str = "auto", datadir: str | None = None, connect_only: bool = False,
-                 max_outbound: int = DEFAULT_MAX_OUTBOUND):
+                 max_outbound: int = DEFAULT_MAX_OUTBOUND, max_connections: int = DEFAULT_MAX_PEER_CONNECTIONS):
         self.state, self.params = state, params
+        self.clock = time.time  # every peer-management time is read here, so tests can drive it
+        self.net_group_key = NetGroupKeyer()
         self.magic = bytes(params.message_start)
         self.gpus = gpus or None
         self.verify_mode = verify_mode
@@ -220,7 +274,15 @@ class ConnectionManager:
         if self.banlist_path:
             self.banned.update(load_banlist(self.banlist_path))
         self.connect_only = connect_only
-        self.max_outbound = max_outbound
+        # -maxconnections is the total: outbound target, and the inbound limit that is left
+        self.max_connections = max_connections
+        self.max_outbound, self.max_inbound = connection_slots(max_connections, max_outbound)
+        self.fetcher = BlockFetcher(state, clock=lambda: self.clock())
+        self._maint_lock = sync.make_lock("cs_maint")  # one maintenance pass at a time
+        self.try_new_outbound = False        # a stale tip allows one outbound peer above the target
+        self.last_tip_update = 0.0
+        self._last_tip: bytes | None = None
+        self._next_extra_check = self._next_stale_check = 0.0
         self.proxies = ProxyTable()          # -proxy / -onion / -onlynet (netbase SetProxy / SetLimited)
         self.whitelist: list = []            # -whitelist subnets (ipaddress networks)
         self.blocks_only = False             # -blocksonly: no transaction relay in either direction
@@ -248,7 +310,38 @@ class ConnectionManager:
             self._id += 1
             return self._id
 
+    @property
+    def max_blocks_in_transit_per_peer(self) -> int:
+        return self.fetcher.per_peer
+
+    @max_blocks_in_transit_per_peer.setter
+    def max_blocks_in_transit_per_peer(self, n: int) -> None:
+        self.fetcher.per_peer = int(n)
+
+    @property
+    def block_download_window(self) -> int:
+        return self.fetcher.window
+
+    @block_download_window.setter
+    def block_download_window(self, n: int) -> None:
+        self.fetcher.window = int(n)
+
+    def set_clock(self, clock) -> None:
+        """Install another time source (tests: a mock clock) and restart the maintenance rhythms,
+        which may already have been counted off the old one."""
+        with self._maint_lock:
+            self.clock = clock
+            self.last_tip_update = self._next_extra_check = self._next_stale_check = 0.0
+
+    def _maintenance_loop(self) -> None:
+        while not self._stop.wait(1.0):
+            try:
+                self.maintain()
+            except Exception as e:  # the keeper of every timeout must outlive one bad pass
+                log.log_printf(f"p2p maintenance pass failed: {type(e).__name__}: {e}")
+
     def start(self) -> None:
+        threading.Thread(target=self._maintenance_loop, name="p2p-maint", daemon=True).start()
         if self.listen_addr is not None:
             srv = socket.socket(socket.AF_INET, socket.SOCK_STREAM)
             srv.setsockopt(socket.SOL_SOCKET, socket.SO_REUSEADDR, 1)
@@ -302,14 +395,14 @@ class ConnectionManager:
             with self._lock:
                 outbound = sum(1 for p in self.peers if not p.inbound)
                 connected = {f"{p.addr[0]}:{p.addr[1]}" for p in self.peers}
-            if outbound >= self.max_outbound or self.addrman.size() == 0:
+            if outbound >= self.max_outbound + (1 if self.try_new_outbound else 0) or self.addrman.size() == 0:
                 continue
             pick = self.addrman.select(exclude=connected)
             if pick is None or self.is_banned(pick[0]) or (self.port and pick == ("127.0.0.1", self.port)):
                 continue
             self.addrman.attempt(*pick)
-            try:
-                self.connect(pick[0], pick[1], timeout=3.0)
+            try:  # an -addnode peer is a manual connection: the outbound eviction rules pass it by
+                self.connect(pick[0], pick[1], timeout=3.0, manual=f"{pick[0]}:{pick[1]}" in self.added_nodes)
             except OSError:
                 continue
 
@@ -323,9 +416,29 @@ class ConnectionManager:
             if not self.network_active or (self.is_banned(addr[0]) and not white):
                 sock.close()  # CConnman::AcceptConnection drops banned / inactive-network peers
                 continue
+            with self._lock:
+                inbound = [p for p in self.peers if p.inbound and not p.closed.is_set()]
+            if len(inbound) >= self.max_inbound and not self._evict_inbound(inbound):
+                log.log_print("net", "failed to find an eviction candidate - connection dropped (full)")
+                sock.close()
+                continue
             self._add(sock, addr, inbound=True, whitebind=white)
 
-    def connect(self, host: str, port: int, timeout: float = 10.0) -> Peer:
+    def _evict_inbound(self, inbound: list[Peer]) -> bool:
+        """AttemptToEvictConnection: close one inbound peer to make room, if one may go."""
+        cands = [EvictionCandidate(p.id, p.connected_at, p.min_ping, p.last_block_time, p.last_tx_time,
+                                   bool(p.info.get("services", 0) & P.NODE_NETWORK), p.relay_txs, p.bloom is not None,
+                                   p.keyed_net_group)
+                 for p in inbound if not p.whitelisted]
+        victim = select_node_to_evict(cands)
+        for p in inbound:
+            if p.id == victim:
+                log.log_print("net", f"evicting inbound peer {p.id} for a new connection")
+                p.close()
+                return True
+        return False
+
+    def connect(self, host: str, port: int, timeout: float = 10.0, manual: bool = False) -> Peer:
         if not self.network_active:
             raise ConnectionError("network is disabled (setnetworkactive false)")
         if not self.allow_dns and not host.endswith(".onion"):
@@ -335,7 +448,7 @@ class ConnectionManager:
                 raise ConnectionError(f"cannot connect to {host}: DNS lookups are disabled (-dns=0)") from None
         sock = self.proxies.connect(host, port, timeout=timeout)  # direct, or SOCKS5 through the net's proxy
         sock.settimeout(None)
-        return self._add(sock, (host, port), inbound=False)
+        return self._add(sock, (host, port), inbound=False, manual=manual)
 
     @property
     def local_services(self) -> int:
@@ -407,12 +520,14 @@ class ConnectionManager:
         with self._lock:
             self.local_addrs.pop((host, port), None)
 
-    def _add(self, sock, addr, inbound: bool, whitebind: bool = False) -> Peer:
+    def _add(self, sock, addr, inbound: bool, whitebind: bool = False, manual: bool = False) -> Peer:
         sock.setsockopt(socket.IPPROTO_TCP, socket.TCP_NODELAY, 1)
         sock.setsockopt(socket.SOL_SOCKET, socket.SO_RCVBUF, max(4096, self.max_receive_buffer))
         sock.setsockopt(socket.SOL_SOCKET, socket.SO_SNDBUF, max(4096, self.max_send_buffer))
         p = Peer(self, sock, addr, inbound)
         p.whitebind = whitebind
+        p.manual = manual
+        self.fetcher.add_peer(p.id)
         with self._lock:
             self.peers.append(p)
         p.thread.start()
@@ -422,6 +537,7 @@ class ConnectionManager:
         with self._lock:
             if p in self.peers:
                 self.peers.remove(p)
+        self.fetcher.remove_peer(p.id)  # its in-flight blocks are asked of the others on the next pass
         self.erase_orphans_for(p.id)  # FinalizeNode -> EraseOrphansFor
 
     # ---------------------------------------------------------------- orphan transactions
@@ -555,6 +671,142 @@ class ConnectionManager:
             for p in list(self.peers):
                 p.close()
 
+    # ---------------------------------------------------------------- maintenance (p2p-maint, once a second)
+    def _drop(self, p: Peer, why: str) -> None:
+        log.log_print("net", f"disconnecting peer {p.id}: {why}")
+        p.close()
+
+    def queue_pings(self) -> None:
+        """The `ping` RPC: every peer's next maintenance pass sends it a ping (fPingQueued)."""
+        with self._lock:
+            for p in self.peers:
+                p.ping_queued = True
+
+    def _inactive(self, p: Peer, now: float) -> str | None:
+        """InactivityCheck (src/net.cpp:1412-1439)."""
+        if now - p.connected_at <= HANDSHAKE_TIMEOUT:
+            return None
+        if not p.last_recv or not p.last_send:
+            return f"no message in the first {HANDSHAKE_TIMEOUT} seconds"
+        if now - p.last_send > TIMEOUT_INTERVAL:
+            return f"socket sending timeout: {now - p.last_send:.0f}s"
+        if now - p.last_recv > TIMEOUT_INTERVAL:
+            return f"socket receive timeout: {now - p.last_recv:.0f}s"
+        if p.ping_nonce and now - p.ping_start >= TIMEOUT_INTERVAL:
+            return f"ping timeout: {now - p.ping_start:.0f}s"
+        if not p.verack:
+            return "version handshake timeout"
+        return None
+
+    def _maybe_ping(self, p: Peer, now: float) -> None:
+        """The ping block of SendMessages: one ping at a time, every PING_INTERVAL or on request.
+        Never waits for the peer: if its sender is busy the ping goes out on a later pass."""
+        if p.ping_nonce or not (p.ping_queued or p.ping_start + PING_INTERVAL < now):
+            return
+        nonce = 0
+        while nonce == 0:
+            nonce = random.getrandbits(64)
+        was = (p.ping_nonce, p.ping_start, p.ping_queued)
+        p.ping_nonce, p.ping_start, p.ping_queued = nonce, now, False  # set first: the pong may be quick
+        try:
+            sent = p.try_send("ping", struct.pack("<Q", nonce))
+        except OSError:
+            p.close()
+            return
+        if not sent:
+            p.ping_nonce, p.ping_start, p.ping_queued = was
+
+    def maintain(self, now: float | None = None) -> None:
+        """One maintenance pass: inactivity and ping timeouts, keep-alive pings, the block-download
+        stall / timeout rules, new block requests, the stale-tip check and the outbound eviction
+        rules. Peers are dropped with Peer.close(), which also frees a sender stuck in sendall."""
+        now = self.clock() if now is None else now
+        spacing = self.params.pow_target_spacing
+        with self._maint_lock:
+            with self._lock:
+                peers = [p for p in self.peers if not p.closed.is_set()]
+            for p in peers:
+                why = self._inactive(p, now)
+                if why is None and p.verack:
+                    self._maybe_ping(p, now)
+                    why = self.fetcher.check_peer(p.id, spacing, now)
+                if why is None and p.verack and not p.inbound and not p.manual:
+                    act = self.fetcher.consider_eviction(p.id, now)
+                    if act == "disconnect":
+                        why = "outbound peer stayed on a chain with less work than ours"
+                    elif act == "getheaders":
+                        try:
+                            p.try_send("getheaders", P.getheaders_payload(P.locator(self.state.chain)))
+                        except OSError:
+                            p.close()
+                if why is not None:
+                    self._drop(p, why)
+            self.request_blocks(now=now)
+            # CheckForStaleTipAndEvictPeers
+            tip = self.state.tip().hash
+            if tip != self._last_tip or not self.last_tip_update:
+                self._last_tip, self.last_tip_update = tip, now
+            if now >= self._next_extra_check:
+                if self._next_extra_check:
+                    self._evict_extra_outbound(now)
+                self._next_extra_check = now + EXTRA_PEER_CHECK_INTERVAL
+            if now > self._next_stale_check:
+                # TipMayBeStale: no new tip for three target spacings and nothing being fetched
+                stale = self.last_tip_update < now - 3 * spacing and self.fetcher.blocks_in_flight() == 0
+                if stale:
+                    log.log_printf(f"Potential stale tip detected, will try using extra outbound peer "
+                                   f"(last tip update: {now - self.last_tip_update:.0f} seconds ago)")
+                self.try_new_outbound = stale
+                self._next_stale_check = now + STALE_CHECK_INTERVAL
+
+    def _evict_extra_outbound(self, now: float) -> None:
+        """EvictExtraOutboundPeers: above the outbound target, the peer whose last block
+        announcement is oldest goes (a tie: the higher id), unless it is young or busy."""
+        with self._lock:
+            out = [p for p in self.peers if not p.inbound and not p.manual and not p.closed.is_set()]
+        if len(out) <= self.max_outbound:
+            return
+        worst, oldest = None, float("inf")
+        for p in out:
+            if self.fetcher.is_protected(p.id):
+                continue
+            t = self.fetcher.last_block_announcement(p.id)
+            if t < oldest or (t == oldest and p.id > worst.id):
+                worst, oldest = p, t
+        if worst is None:
+            return
+        if now - worst.connected_at > MINIMUM_CONNECT_TIME and self.fetcher.blocks_in_flight(worst.id) == 0:
+            self._drop(worst, f"extra outbound peer (last block announcement at {oldest:.0f})")
+            self.try_new_outbound = False
+        else:
+            log.log_print("net", f"keeping outbound peer {worst.id} chosen for eviction")
+
+    def request_blocks(self, own: "Peer | None" = None, now: float | None = None) -> None:
+        """Ask every handshaken peer for the next blocks it can serve, up to the per-peer limit.
+        `own` is the calling thread's own peer: it may wait for its socket; the others are only
+        tried, and a request that cannot be written now is freed for the next pass."""
+        with self._lock:
+            peers = [p for p in self.peers if p.verack and not p.closed.is_set()]
+        if own is not None and own in peers:
+            peers.remove(own)
+            peers.insert(0, own)
+        for p in peers:
+            blocks, _ = self.fetcher.assign(p.id, now)
+            if not blocks:
+                continue
+            payload = P.inv_payload([(P.MSG_BLOCK | P.MSG_WITNESS_FLAG, h) for h, _ in blocks])
+            try:
+                if p is own:
+                    p.send("getdata", payload)
+                    sent = True
+                else:
+                    sent = p.try_send("getdata", payload)
+            except OSError:
+                sent = False
+                p.close()
+            if not sent:
+                self.fetcher.unassign(p.id, [h for h, _ in blocks])
+
     # ---------------------------------------------------------------- relay
     def announce_block(self, header, block=None) -> None:
         """New tip: `cmpctblock` to high-bandwidth BIP152 peers, `headers` to peers that asked for
@@ -633,7 +885,7 @@ class ConnectionManager:
         peer.send("sendcmpct", struct.pack("<?Q", False, 2))  # BIP152 v2, low-bandwidth
         if not peer.inbound:
             peer.send("getaddr")
-        self.request_headers(peer)
+        self.request_headers(peer, initial=True)
 
     # ---------------------------------------------------------------- addresses (N4)
     def on_addr(self, peer: Peer, p: bytes) -> None:
@@ -728,8 +980,7 @@ class ConnectionManager:
             peer.send("getdata", P.inv_payload([(P.MSG_BLOCK | P.MSG_WITNESS_FLAG, self.state.block_hash(cb.header))]))
             return
         REGISTRY.inc("p2p_cmpct_reconstructed_total", 1)
-        self.state.arm_reorg_guard(self.peer_count())
-        st = self.state.process_new_block(blk)
+        st = self._process_block(peer, blk)
         if not st.ok and st.reject != "duplicate":
             peer.misbehaving(st.dos or 0, f"invalid compact block: {st.reject}")
 
@@ -765,10 +1016,39 @@ class ConnectionManager:
         peer.send("pong", p[:8])
 
     def on_pong(self, peer: Peer, p: bytes) -> None:
-        pass
+        """NetMsgType::PONG: only the matching nonce ends the outstanding ping. Anything else is
+        logged and ignored, without a ban score, as the reference does."""
+        now = self.clock()
+        problem = None
+        if len(p) < 8:
+            problem = "Short payload"
+        else:
+            (nonce,) = struct.unpack_from("<Q", p, 0)
+            if not peer.ping_nonce:
+                problem = "Unsolicited pong without ping"
+            elif nonce == peer.ping_nonce:
+                peer.ping_nonce = 0
+                rtt = now - peer.ping_start
+                if rtt >= 0:
+                    peer.ping_time = rtt
+                    peer.min_ping = min(peer.min_ping, rtt)
+                else:
+                    problem = "Timing mishap"
+            elif nonce == 0:
+                problem = "Nonce zero"  # the ping stays outstanding (the reference gives it up here)
+            else:
+                problem = "Nonce mismatch"
+        if problem is not None:
+            log.log_print("net", f"pong peer={peer.id}: {problem}, {len(p)} bytes")
 
-    def request_headers(self, peer: Peer) -> None:
-        peer.send("getheaders", P.getheaders_payload(P.locator(self.state.chain)))
+    def request_headers(self, peer: Peer, initial: bool = False) -> None:
+        loc = P.locator(self.state.chain)
+        if initial and len(loc) > 1:
+            # the first request starts one below our best header (src/net_processing.cpp:3372-3380):
+            # a peer that is up to date then answers with at least that header, which tells the
+            # block fetcher what the peer has even when it has nothing new for us
+            loc = loc[1:]
+        peer.send("getheaders", P.getheaders_payload(loc))
 
     def on_getheaders(self, peer: Peer, p: bytes) -> None:
         loc, stop = P.parse_getheaders(p)
@@ -793,11 +1073,13 @@ class ConnectionManager:
         headers = _core.headers_msg_decode(p, self.params.kawpow_activation_time)
         if not headers:
             return
+        last = self.state.block_hash(headers[-1])
         with self.sync_lock:
             chain = self.state.chain
             if chain.find(headers[0].prev) is None:  # unconnecting headers: ask from our locator
                 self.request_headers(peer)
                 return
+            new_header = chain.find(last) is None
             self.state.arm_reorg_guard(self.peer_count())
             t0 = time.perf_counter()
             res = None
@@ -820,10 +1102,9 @@ class ConnectionManager:
                 peer.misbehaving(100 if res["reject"]["reason"] in ("high-hash", "invalid-mix-hash", "bad-diffbits")
                                  else 20, f"invalid header: {res['reject']}")
                 return
-        want = [self.state.block_hash(h) for h in headers]
-        want = [h for h in want if h not in self.state.block_pos]
-        for k in range(0, len(want), 128):
-            peer.send("getdata", P.inv_payload([(P.MSG_BLOCK | P.MSG_WITNESS_FLAG, h) for h in want[k:k + 128]]))
+        # the peer has this chain; the fetcher decides which of its blocks to ask of whom
+        self.fetcher.update_availability(peer.id, last, announced=new_header)
+        self.request_blocks(own=peer)
         if len(headers) == P.MAX_HEADERS_RESULTS:
             self.request_headers(peer)
 
@@ -835,13 +1116,19 @@ class ConnectionManager:
         if any(t & ~P.MSG_WITNESS_FLAG == P.MSG_BLOCK and self.state.chain.find(h) is None for t, h in items):
             self.request_headers(peer)
         want = []
+        announced = False
         for t, h in items:
+            if t & ~P.MSG_WITNESS_FLAG == P.MSG_BLOCK:
+                self.fetcher.update_availability(peer.id, h)  # a known header, or remembered until it is
+                announced = True
             if t & ~P.MSG_WITNESS_FLAG == P.MSG_TX:
                 peer.known_txs.add(h)
                 if h not in self.state.mempool:
                     want.append((P.MSG_TX | P.MSG_WITNESS_FLAG, h))
         if want:
             peer.send("getdata", P.inv_payload(want))
+        if announced:
+            self.request_blocks(own=peer)
 
     def on_tx(self, peer: Peer, p: bytes) -> None:
         """AcceptToMemoryPool for a relayed tx (UTXO set, scripts, fees); accepted transactions
@@ -860,6 +1147,7 @@ class ConnectionManager:
         self.state.last_replaced = []
         ok, reason, _ = self.state.accept_to_mempool(tx)
         if ok:
+            peer.last_tx_time = self.clock()
             if self.extra_txn.maxlen:  # transactions a replacement pushed out stay usable for compact blocks
                 self.extra_txn.extend(self.state.last_replaced)
             self.process_orphans(txid, len(tx.vout))
@@ -929,8 +1217,28 @@ class ConnectionManager:
 
     def on_block(self, peer: Peer, p: bytes) -> None:
         blk = _core.Block.deserialize(p, self.params.kawpow_activation_time)
-        self.state.arm_reorg_guard(self.peer_count())
-        st = self.state.process_new_block(blk)
+        st = self._process_block(peer, blk)
         REGISTRY.inc("p2p_blocks_received_total", 1, ok=st.ok)
         if not st.ok and st.reject != "duplicate":
             peer.misbehaving(st.dos or 0, f"invalid block: {st.reject}")
+
+    def _process_block(self, peer: Peer, blk):
+        """A whole block from a peer, asked for or not: its in-flight record is cleared whoever it
+        was asked of, it is validated, and the freed slot is filled with the next request."""
+        h = self.state.block_hash(blk.header)
+        self.state.arm_reorg_guard(self.peer_count())
+        st = self.state.process_new_block(blk)
+        if st.ok:
+            peer.last_block_time = self.clock()
+        elif st.reject != "duplicate" and h in self.state.block_pos:
+            # stored, so its transactions are the header's own, and it failed to connect: what
+            # builds on it is not fetched. A block refused before it was stored (a bad merkle root,
+            # duplicate transactions, a bad witness commitment) says nothing about the real block
+            # with this header, which anybody can wrap around other transactions: it stays wanted.
+            self.fetcher.mark_rejected(h)
+        # the record goes only now that the block is stored: a pass of another peer's thread in
+        # between would find it neither in flight nor here, and ask for it a second time
+        self.fetcher.received(h)
+        self.fetcher.update_availability(peer.id, h, announced=False)
+        self.request_blocks(own=peer)
+        return st

@@ -630,7 +630,7 @@ class Node:
         """-listen / -port / -bind / -connect (CConnman subset, net/p2p.py). Listening is opt-in
         (-listen or -port) so tests and benches never fight over the default port."""
         from .chain.state import ValidationInterface
-        from .net.p2p import ConnectionManager
+        from .net.p2p import DEFAULT_MAX_PEER_CONNECTIONS, ConnectionManager
 
         a = self.args
         from .net.netbase import parse_host_port
@@ -648,8 +648,8 @@ class Node:
             return
         self.connman = ConnectionManager(self.state, self.params, gpus=self.gpus, listen=listen,
                                          verify_mode=a.get("p2pverifymode", "auto"), datadir=self.datadir,
-                                         connect_only=bool(connect),
-                                         max_outbound=a.get_int("maxconnections", 8) if not connect else 0)
+                                         connect_only=bool(connect),  # -connect: no automatic outbound peers
+                                         max_connections=a.get_int("maxconnections", DEFAULT_MAX_PEER_CONNECTIONS))
         self.connman.proxies.configure(a)
         self.connman.extra_binds = binds
         self.connman.max_receive_buffer = a.get_int("maxreceivebuffer", 5000) * 1000
@@ -718,7 +718,7 @@ class Node:
         for c in connect:
             host, _, port = c.rpartition(":")
             try:
-                cm.connect(host or "127.0.0.1", int(port))
+                cm.connect(host or "127.0.0.1", int(port), manual=True)
             except OSError as e:
                 log.log_printf(f"connect to {c} failed: {e}")
 

@@ -763,14 +763,15 @@ def register(table, node) -> None:  # noqa: C901 — one table, like the referen
                 raise RPCError(-23, "Error: Node already added")
             cm.added_nodes.append(p[0])
         host, _, port = str(p[0]).rpartition(":")
-        cm.connect(host or "127.0.0.1", int(port or params.default_port))
+        cm.connect(host or "127.0.0.1", int(port or params.default_port), manual=True)
         return None
 
     def rpc_ping(p):
-        """ping — request a pong from every peer."""
+        """ping — queue a ping to every peer; the results are getpeerinfo's pingtime and pingwait."""
         cm = _cm()
-        for x in list(cm.peers) if cm else []:
-            x.send("ping", struct.pack("<Q", int(time.time() * 1e6)))
+        if cm is not None:
+            cm.queue_pings()
+            cm.maintain()  # one maintenance pass now, so the pings go out promptly
         return None
 
     for name, fn, args in [("getconnectioncount", rpc_getconnectioncount, ()), ("getpeerinfo", rpc_getpeerinfo, ()),

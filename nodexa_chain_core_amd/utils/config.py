@@ -9,6 +9,10 @@ network selection from -regtest / -testnet (SelectParams).
 
 New engine flags: -gpus=0,1,.. -kawpowactivationtime= -equihash
 -gpuintensity= -dagcache= -gpufailrate= -dropshare= -strictheight -dbformat=leveldb|journal
+
+-maxconnections=<n>: maintain at most <n> connections to peers in total (default 125), as in the
+reference: up to min(8, n) of them outbound, and n less the outbound slots and one more for
+inbound peers; at that limit a new inbound peer takes the place of an evictable one or is refused.
 """
 from __future__ import annotations
 
