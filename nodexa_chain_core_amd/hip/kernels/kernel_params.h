@@ -192,6 +192,34 @@ struct KawpowHashParams {
     struct FastMod32 items;
 };
 
+// Period-agnostic search / batch hash (kawpow_anyperiod.hip): KawpowSearchParams / KawpowHashParams
+// plus the period's program as data and the L1. A workgroup of kawpow_search_any is 256 threads
+// and covers `granule` nonces; the launch is num_nonces / granule workgroups.
+struct KawpowAnySearchParams {
+    const void* dag;           // 2048-bit items (16 x uint4 each)
+    struct KawpowResults* results;
+    uint64_t start_nonce;
+    uint64_t target;           // share if bswap64(final[0..1]) <= target (upper 64 bits, BE)
+    uint32_t header[8];        // header hash words (storage order)
+    struct FastMod32 items;    // modulo by number of 2048-bit items (full_items / 2)
+    const uint32_t* program;   // KV_PROG_WORDS words: the one period of this launch
+    const uint32_t* l1;        // 4096-word L1 (first 16 KiB of the DAG)
+    const uint32_t* gen_word;  // stale-work abort as in KawpowSearchParams; nullptr: never abort
+    uint32_t generation;
+    uint32_t granule;          // nonces per workgroup, a multiple of 64
+};
+
+struct KawpowAnyHashParams {
+    const void* dag;                  // full DAG (2048-bit items)
+    const struct KawpowVerifyJob* jobs;
+    uint32_t* out;                    // per job: mix[8] then final[8]
+    const uint32_t* program;          // KV_PROG_WORDS words: the period of every job
+    const uint32_t* l1;               // 4096-word L1
+    uint32_t num_jobs;
+    uint32_t pad;
+    struct FastMod32 items;
+};
+
 // Classic Ethash hashimoto over the resident DAG (ethash_hashimoto.hip): jobs are (header hash,
 // nonce) pairs (KawpowVerifyJob, block_number unused); out per job: mix[8] then final[8].
 struct EthashHashParams {

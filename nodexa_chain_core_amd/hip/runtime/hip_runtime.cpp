@@ -313,6 +313,55 @@ PYBIND11_MODULE(_hip, m) {
         if (grid == 0) return;
         k.launch_bytes(dim3(grid), dim3(block), 0, as_stream(stream), &p, sizeof(p));
     });
+    // Period-agnostic search (kawpow_anyperiod.hip): launch_kawpow_search's arguments plus the
+    // period's 64 program words and the 4096-word L1 on the device. `granule` is the nonce
+    // granularity of the launch (the block of the specialised variant it stands in for); the
+    // kernel's own workgroup is always 256 threads and walks a granule in passes.
+    m.def("launch_kawpow_search_any", [](const Kernel& k, uintptr_t dag, uint32_t dag_items2048, uintptr_t results,
+                                         const py::bytes& header, uint64_t start_nonce, uint64_t target,
+                                         uint64_t num_nonces, uintptr_t stream, uintptr_t program, uintptr_t l1,
+                                         uint32_t granule, uintptr_t gen_word, uint32_t generation) {
+        if (k.max_threads != 256) throw std::invalid_argument("kawpow_search_any is a 256-thread kernel");
+        if (granule == 0 || granule % 64 || granule > 4096)
+            throw std::invalid_argument("search granule must be a multiple of 64, at most 4096");
+        if (num_nonces % granule) throw std::invalid_argument("num_nonces must be a multiple of the granule");
+        if (dag == 0 || program == 0 || l1 == 0 || results == 0)
+            throw std::invalid_argument("kawpow_search_any needs the DAG, the program, the L1 and a share ring");
+        KawpowAnySearchParams p{};
+        p.dag = reinterpret_cast<const void*>(dag);
+        p.results = reinterpret_cast<KawpowResults*>(results);
+        p.start_nonce = start_nonce;
+        p.target = target;
+        load_words(header, p.header);
+        p.items = make_fastmod(dag_items2048);
+        p.program = reinterpret_cast<const uint32_t*>(program);
+        p.l1 = reinterpret_cast<const uint32_t*>(l1);
+        p.gen_word = reinterpret_cast<const uint32_t*>(gen_word);
+        p.generation = generation;
+        p.granule = granule;
+        const uint64_t grid = num_nonces / granule;
+        if (grid == 0 || grid > 0x7fffffffULL) throw std::invalid_argument("bad search grid");
+        k.launch_bytes(dim3(unsigned(grid)), dim3(256), 0, as_stream(stream), &p, sizeof(p));
+    }, py::arg("kernel"), py::arg("dag"), py::arg("dag_items2048"), py::arg("results"), py::arg("header"),
+       py::arg("start_nonce"), py::arg("target"), py::arg("num_nonces"), py::arg("stream"), py::arg("program"),
+       py::arg("l1"), py::arg("granule"), py::arg("gen_word") = 0, py::arg("generation") = 0);
+    m.def("launch_kawpow_hash_any", [](const Kernel& k, uintptr_t dag, uint32_t dag_items2048, uintptr_t jobs,
+                                       uint32_t num_jobs, uintptr_t out, uintptr_t program, uintptr_t l1,
+                                       uintptr_t stream) {
+        if (k.max_threads != 256) throw std::invalid_argument("kawpow_hash_any is a 256-thread kernel");
+        if (dag == 0 || program == 0 || l1 == 0) throw std::invalid_argument("kawpow_hash_any needs the DAG, the program and the L1");
+        KawpowAnyHashParams p{};
+        p.dag = reinterpret_cast<const void*>(dag);
+        p.jobs = reinterpret_cast<const KawpowVerifyJob*>(jobs);
+        p.out = reinterpret_cast<uint32_t*>(out);
+        p.program = reinterpret_cast<const uint32_t*>(program);
+        p.l1 = reinterpret_cast<const uint32_t*>(l1);
+        p.num_jobs = num_jobs;
+        p.items = make_fastmod(dag_items2048);
+        const unsigned grid = (num_jobs + 255) / 256;
+        if (grid == 0) return;
+        k.launch_bytes(dim3(grid), dim3(256), 0, as_stream(stream), &p, sizeof(p));
+    });
     // Classic Ethash hashimoto (ethash_hashimoto.hip): seed -> mix (per_row jobs per 16-lane row,
     // 16 rows per block) -> final, in order on one stream; `seeds` holds n x 64 bytes. Search mode
     // (search_header given, jobs ignored): job i is (header, start_nonce + i); with a boundary, the

@@ -200,7 +200,14 @@ def main(argv: list[str] | None = None) -> int:
     from .service import make_rank_device
 
     cpu = a.get_bool("cpu", False)
-    backend = make_rank_device(cpu, None if cpu else a.get_int("gpu", 0), window=a.get_int("minerwindow", 4096))
+    from ..utils.config import kawpow_jit_mode
+
+    try:
+        jit_mode = kawpow_jit_mode(a)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    backend = make_rank_device(cpu, None if cpu else a.get_int("gpu", 0), window=a.get_int("minerwindow", 4096),
+                               jit_mode=jit_mode)
     m = RemoteMiner(rpc, backend, window=a.get_int("minerwindow", 1 << 25), rank=a.get_int("minerrank", 0))
     blocks = a.get_int("blocks", 0)
     stats = m.run(max_blocks=blocks or None)

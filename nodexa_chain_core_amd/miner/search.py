@@ -151,6 +151,7 @@ class SlotResult:
     aborted: int = 0
     algo: int = ALGO_KAWPOW
     end_ms: float = 0.0  # device clock: the window's end, ms after the device's first window began
+    kernel: str = ""     # KawPow on a GPU: "jit" (per-period compiled kernel) or "generic" (period-agnostic)
 
 
 class DeviceHung(RuntimeError):
@@ -166,16 +167,24 @@ class GpuSearchDevice:
 
     `collective_dag`: build DAGs sharded over the current process group and all-gather them
     (parallel/dag.py); every rank must then prepare the same epoch at the same step, which the
-    mining service guarantees (all ranks act on the same broadcast work packet)."""
+    mining service guarantees (all ranks act on the same broadcast work packet).
+
+    `jit_mode` (-kawpowjit, ops/kawpow.KawpowSearcher): "wait" stalls the loop in `submit` until a
+    new period's kernel is compiled; "auto" runs such windows on the period-agnostic kernel and
+    swaps to the compiled one between two windows; "off" never compiles."""
 
     name = "gpu"
     MAX_EPOCHS = 2  # current + next (two 4 GiB DAGs are ~3 % of 288 GB)
 
-    def __init__(self, device: int = 0, collective_dag: bool = False):
+    def __init__(self, device: int = 0, collective_dag: bool = False, jit_mode: str = "wait"):
         import torch
 
-        from ..ops import runtime
+        from ..ops import jit, runtime
 
+        if jit_mode not in jit.JIT_MODES:
+            raise ValueError(f"kawpow jit mode must be one of {', '.join(jit.JIT_MODES)}, not {jit_mode!r}")
+        self.jit_mode = jit_mode
+        self.kernel_kind = ""  # kernel of the last window submitted
         runtime.require_gpu()
         self.device = int(device)
         self.collective_dag = collective_dag
@@ -288,7 +297,7 @@ class GpuSearchDevice:
             s = self.searchers.get(epoch)
             if s is None:
                 with self.torch.cuda.device(self.device):
-                    s = KawpowSearcher(ep, height, prefetch_next=True)
+                    s = KawpowSearcher(ep, height, prefetch_next=True, jit_mode=self.jit_mode)
                 self.searchers[epoch] = s
             else:
                 s.set_block(height)
@@ -319,7 +328,8 @@ class GpuSearchDevice:
                      results=ring, gen_word=self.gen_ptr, generation=self.generation)
             self.host[slot].copy_(ring, non_blocking=True)
             self.events[slot].record(st)
-        self.meta[slot] = (work, start, count, b)
+        self.kernel_kind = s.kernel_kind
+        self.meta[slot] = (work, start, count, b, s.kernel_kind)
 
     def wait(self, slot: int, timeout_s: float | None = None) -> SlotResult:
         from ..ops.kawpow import parse_results
@@ -332,13 +342,13 @@ class GpuSearchDevice:
                     raise DeviceHung(f"gpu{self.device}: search window did not finish in {timeout_s:.0f}s")
                 time.sleep(0.0005)
         ev.synchronize()
-        work, start, count, block = self.meta[slot]
+        work, start, count, block, kind = self.meta[slot]
         self.meta[slot] = None
         shares, _n, skipped = parse_results(self.host[slot].numpy().tobytes(), self.h.KAWPOW_MAX_SHARES)
         shares = [x for x in shares if _core.hash_le(x.final_hash, work.boundary)]
         hashes = max(0, count - skipped * block)
         return SlotResult(work.job_id, start, count, hashes, shares, self.starts[slot].elapsed_time(ev), skipped,
-                          ALGO_KAWPOW, self.anchor.elapsed_time(ev))
+                          ALGO_KAWPOW, self.anchor.elapsed_time(ev), kind)
 
     def abort(self) -> None:
         """Make every queued or running window stale (its remaining workgroups exit at start)."""

@@ -76,6 +76,8 @@ _SHARE = {ALGO_KAWPOW: struct.Struct("<Q32s32s"),        # nonce, mix, final
 RECORD_PAYLOAD = max(MAX_SHARES[a] * s.size for a, s in _SHARE.items())  # 5536
 RECORD_SIZE = _REC_HEAD.size + RECORD_PAYLOAD                           # 5592
 STATUS_RESULT, STATUS_ALIVE, STATUS_VOTE = 1, 2, 4  # VOTE: next-epoch light cache ready
+STATUS_KERNEL_JIT, STATUS_KERNEL_GENERIC = 8, 16     # the KawPow kernel of the record's window (neither: not a GPU KawPow window)
+_KERNEL_BITS = {"jit": STATUS_KERNEL_JIT, "generic": STATUS_KERNEL_GENERIC}
 
 
 class CollectiveError(RuntimeError):
@@ -101,6 +103,7 @@ class RankRecord:
     has_result: bool = False
     alive: bool = True
     device: int = -1
+    kernel: str = ""  # "jit" / "generic": the KawPow kernel of this window on a GPU rank
 
 
 def _as_record(r) -> RankRecord:
@@ -119,6 +122,7 @@ def pack_record(res: SlotResult | None, *, coll_ms: float = 0.0, failures: int =
     if res is None:
         _REC_HEAD.pack_into(out, 0, 0, 0, 0, 0, 0, 0, int(coll_ms * 1e3), failures, lo, n, status, device)
         return bytes(out)
+    status |= _KERNEL_BITS.get(getattr(res, "kernel", ""), 0)
     fmt = _SHARE[res.algo]
     shares = res.shares[:MAX_SHARES[res.algo]]
     _REC_HEAD.pack_into(out, 0, res.job_id, res.hashes, len(shares), res.algo, min(int(res.device_ms * 1e3), 2**32 - 1),
@@ -160,7 +164,8 @@ def unpack_record(raw: bytes) -> RankRecord:
         else:
             shares.append(LegacyShare(*vals))
     return RankRecord(job, hashes, shares, algo, dev_us / 1e3, aborted, coll_us / 1e3, failures,
-                      list(range(lo, lo + nep)), bool(status & STATUS_RESULT), bool(status & STATUS_ALIVE), device)
+                      list(range(lo, lo + nep)), bool(status & STATUS_RESULT), bool(status & STATUS_ALIVE), device,
+                      "jit" if status & STATUS_KERNEL_JIT else "generic" if status & STATUS_KERNEL_GENERIC else "")
 
 
 class Comm:
@@ -652,6 +657,7 @@ class MiningService:
         self.hashes_total = 0
         self.rank_hashes: dict[int, int] = {}
         self.rank_info_raw: dict[int, dict] = {}
+        self.kernel_windows = {"jit": 0, "generic": 0}  # GPU KawPow windows by kernel, all ranks (rank 0 only)
         self.rank_rates: dict[int, RateMeter] = {}
         self.steps = 0
         self.membership = 0
@@ -760,13 +766,18 @@ class MiningService:
             for i, rec_i in enumerate(records):
                 self.rank_hashes[i] = self.rank_hashes.get(i, 0) + rec_i.hashes
                 self.rank_rates.setdefault(i, RateMeter()).add(rec_i.hashes, now)
-                info = self.rank_info_raw.setdefault(i, {"aborted": 0, "windows": 0})
+                info = self.rank_info_raw.setdefault(i, {"aborted": 0, "windows": 0, "jit_windows": 0,
+                                                         "generic_windows": 0})
                 info.update(alive=rec_i.alive, failures=rec_i.failures, epochs=rec_i.epochs, device=rec_i.device,
                             coll_ms=rec_i.coll_ms)
                 if rec_i.has_result:
                     info["windows"] += 1
                     info["aborted"] += rec_i.aborted
                     info.update(algo=rec_i.algo, device_ms=rec_i.device_ms)
+                    if rec_i.kernel:
+                        info["kernel"] = rec_i.kernel
+                        info[rec_i.kernel + "_windows"] += 1
+                        self.kernel_windows[rec_i.kernel] += 1
             self.leader.on_results(records)
             if self.world_size == 1 and not self.dev_alive and hasattr(self.leader, "fail"):
                 self.leader.fail("no mining device left (all evicted): " + self.last_error)
@@ -814,6 +825,9 @@ class MiningService:
                 "collective_ms": round(info.get("coll_ms", 0.0), 3),
                 "aborted_workgroups": info.get("aborted", 0),
                 "windows": info.get("windows", 0),
+                "kernel": info.get("kernel", ""),
+                "generic_windows": info.get("generic_windows", 0),
+                "jit_windows": info.get("jit_windows", 0),
                 "failures": info.get("failures", 0),
             })
         return out
@@ -913,6 +927,7 @@ class Miner:
         self.generating = False
         self._last_hashes = 0
         self._last_shares = 0
+        self._last_kernel_windows = {"jit": 0, "generic": 0}
 
     @classmethod
     def local(cls, state, *, window: int = 4096, fail_rate: float = 0.0, drop_rate: float = 0.0,
@@ -946,6 +961,10 @@ class Miner:
         if s > self._last_shares:
             self.metrics.inc("miner_shares_total", s - self._last_shares, worker="service")
         self._last_hashes, self._last_shares = h, s
+        for kind, n in self.service.kernel_windows.items():
+            if n > self._last_kernel_windows[kind]:
+                self.metrics.inc(f"miner_kawpow_{kind}_windows_total", n - self._last_kernel_windows[kind], worker="service")
+                self._last_kernel_windows[kind] = n
 
     def generate(self, script_pubkey: bytes, nblocks: int, max_tries: int = 1_000_000) -> list[str]:
         """generateBlocks: the new block hashes (display hex), mined by the service."""
@@ -1007,8 +1026,32 @@ def spawn_followers(gpus: list[int], port: int, cpu: bool = False, extra_env: di
     return procs
 
 
+def follower_env(*, timeout: float, watchdog, max_failures: int, fail_rate: float, drop_rate: float,
+                 jit_mode: str = "wait", window=None) -> dict[str, str]:
+    """The node's miner flags as the environment of the follower ranks it spawns (follower_main
+    reads them back): -minercollectivetimeout, -minerwatchdog, -minermaxfailures, -gpufailrate,
+    -dropshare, -kawpowjit and, when set, -gpuintensity."""
+    env = {"NODEXA_MINER_COLLECTIVE_TIMEOUT": str(timeout), "NODEXA_MINER_WATCHDOG": str(watchdog),
+           "NODEXA_MINER_MAXFAILURES": str(max_failures), "NODEXA_MINER_FAILRATE": str(fail_rate),
+           "NODEXA_MINER_DROPSHARE": str(drop_rate), "NODEXA_MINER_KAWPOWJIT": jit_mode}
+    if window:
+        env["NODEXA_MINER_WINDOW"] = str(window)
+    return env
+
+
+def follower_jit_mode() -> str:
+    """-kawpowjit as the node handed it to this follower rank (validated: the node already did)."""
+    from ..utils.config import KAWPOW_JIT_MODES
+
+    mode = os.environ.get("NODEXA_MINER_KAWPOWJIT", "wait") or "wait"
+    if mode not in KAWPOW_JIT_MODES:
+        raise ValueError(f"NODEXA_MINER_KAWPOWJIT={mode}: expected one of {', '.join(KAWPOW_JIT_MODES)}")
+    return mode
+
+
 def make_rank_device(cpu: bool, device_index: int | None = None, collective_dag: bool = False, window: int = 4096,
-                     fail_rate: float = 0.0, drop_rate: float = 0.0, seed: int = 0, eq_window: int = 1):
+                     fail_rate: float = 0.0, drop_rate: float = 0.0, seed: int = 0, eq_window: int = 1,
+                     jit_mode: str = "wait"):
     """This rank's RankDevice: GPU KawPow + GPU Equihash (built on first use) + GPU X16R, or the
     host equivalents; -gpufailrate / -dropshare wrap it."""
     from .equihash_search import EquihashCpuDevice
@@ -1021,7 +1064,7 @@ def make_rank_device(cpu: bool, device_index: int | None = None, collective_dag:
         from .search import GpuSearchDevice, LegacyGpuDevice
 
         idx = int(device_index or 0)
-        dev = RankDevice(GpuSearchDevice(idx, collective_dag=collective_dag),
+        dev = RankDevice(GpuSearchDevice(idx, collective_dag=collective_dag, jit_mode=jit_mode),
                          equihash_factory=lambda: EquihashGpuDevice(idx), legacy=LegacyGpuDevice(idx))
     if fail_rate or drop_rate:
         dev = FaultInjectingDevice(dev, fail_rate, drop_rate, seed=seed)
@@ -1042,7 +1085,8 @@ def follower_main() -> int:
     w = W.get()
     dev = make_rank_device(cpu, w.device.index if not cpu else None, collective_dag=w.collective, window=window,
                            fail_rate=float(os.environ.get("NODEXA_MINER_FAILRATE", "0") or 0),
-                           drop_rate=float(os.environ.get("NODEXA_MINER_DROPSHARE", "0") or 0), seed=w.rank)
+                           drop_rate=float(os.environ.get("NODEXA_MINER_DROPSHARE", "0") or 0), seed=w.rank,
+                           jit_mode=follower_jit_mode())
     hang = int(os.environ.get("NODEXA_MINER_HANG_AFTER", "0"))
     if hang > 0:  # fault injection for the failure-handling tests
         from .search import HangingDevice

@@ -35,7 +35,7 @@ from .rpc import (methods, methods_assets, methods_ext, methods_index, methods_m
                   methods_wallet_ext)
 from .rpc.server import RPCServer, RPCTable, delete_cookie, make_cookie
 from .utils import log, metrics
-from .utils.config import ArgsManager, gpu_list
+from .utils.config import ArgsManager, gpu_list, kawpow_jit_mode
 
 _core = core()
 
@@ -388,6 +388,10 @@ class Node:
         from .parallel import world as W
 
         cpu = not self.gpus
+        try:
+            jit_mode = kawpow_jit_mode(a)
+        except ValueError as e:
+            raise SystemExit(str(e))
         timeout = float(a.get("minercollectivetimeout", "60"))
         fail, drop = float(a.get("gpufailrate", "0") or 0), float(a.get("dropshare", "0") or 0)
         self.miner_procs = []
@@ -406,12 +410,9 @@ class Node:
                     sk.bind(("127.0.0.1", 0))
                     port = sk.getsockname()[1]
                 os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-                env = {"NODEXA_MINER_COLLECTIVE_TIMEOUT": str(timeout),
-                       "NODEXA_MINER_WATCHDOG": a.get("minerwatchdog", "120"),
-                       "NODEXA_MINER_MAXFAILURES": str(a.get_int("minermaxfailures", 3)),
-                       "NODEXA_MINER_FAILRATE": str(fail), "NODEXA_MINER_DROPSHARE": str(drop)}
-                if a.get("gpuintensity"):
-                    env["NODEXA_MINER_WINDOW"] = a.get("gpuintensity")
+                env = MS.follower_env(timeout=timeout, watchdog=a.get("minerwatchdog", "120"),
+                                      max_failures=a.get_int("minermaxfailures", 3), fail_rate=fail, drop_rate=drop,
+                                      jit_mode=jit_mode, window=a.get("gpuintensity"))
                 self.miner_procs = MS.spawn_followers(gpus, port, cpu=cpu, extra_env=env)
             W.init(use_gpu=not cpu, timeout_s=max(int(timeout), W.rendezvous_timeout()),
                    device_index=None if cpu else gpus[0],
@@ -420,7 +421,7 @@ class Node:
         w = W.get()
         window = a.get_int("gpuintensity", 4096 if cpu else 1 << 25)
         dev = MS.make_rank_device(cpu, None if cpu else w.device.index, collective_dag=w.collective, window=window,
-                                  fail_rate=fail, drop_rate=drop, seed=0)
+                                  fail_rate=fail, drop_rate=drop, seed=0, jit_mode=jit_mode)
         leader = MS.ChainLeader(self.state, target_bits=a.get_int("minertargetbits", 0),
                                 state_path=os.path.join(self.datadir, "miner_state.json") if self.datadir else None)
         log.log_printf(f"miner service: {w.world_size} rank(s), backend {w.backend}, "

@@ -125,6 +125,127 @@ def get(period: int, defines: tuple[str, ...] | None = None) -> str:
     return prefetch(period, defines).result()
 
 
+def ready(period: int, defines: tuple[str, ...] | None = None) -> str | None:
+    """The path of `period`'s code object if it can be loaded now, else None; never blocks and
+    never starts a compile. Ready = its compile future finished without error, or (no compile
+    running in this process) the cache file exists."""
+    defines = DEFAULT_DEFINES if defines is None else tuple(defines)
+    with _lock:
+        fut = _inflight.get((period, defines))
+    if fut is not None:
+        if not fut.done():
+            return None
+        if fut.exception() is None:
+            return fut.result()
+    path = object_path(period, defines)
+    return path if os.path.exists(path) else None
+
+
+DEFAULT_BLOCK = 256  # NODEXA_KAWPOW_BLOCK (kernel_params.h): the template's KP_BLOCK when no define sets it
+
+
+def granule_for(dag_bytes: int, defines: tuple[str, ...] | None = None) -> int:
+    """Nonce granularity of a search launch over a DAG of `dag_bytes`: the KP_BLOCK of the variant
+    `defines_for` picks, i.e. the workgroup size of the specialised kernel. The period-agnostic
+    kernel cuts its launches the same way, so a window is the same whichever kernel runs it."""
+    for d in defines_for(dag_bytes, defines):
+        if d.startswith("KP_BLOCK="):
+            return int(d.split("=", 1)[1])
+    return DEFAULT_BLOCK
+
+
+JIT_MODES = ("wait", "auto", "off")
+JIT_FLAG_HINT = "-kawpowjit=auto (or off) mines on the period-agnostic kernel without the compiler"
+
+
+class KernelChoice:
+    """What `KernelChooser.choose` decided for one period."""
+    __slots__ = ("kind", "path", "log")
+
+    def __init__(self, kind: str, path: str | None = None, log: str | None = None):
+        self.kind = kind  # "jit": load `path`; "generic": the period-agnostic kernel
+        self.path = path
+        self.log = log    # a line to log now (at most one per period), or None
+
+    def __repr__(self) -> str:
+        return f"KernelChoice({self.kind!r}, {self.path!r}, {self.log!r})"
+
+
+class KernelChooser:
+    """Which search kernel a period runs on: the per-period compiled one ("jit") or the
+    period-agnostic one ("generic"). No GPU, no compiler: it only sees two callables.
+
+      ready(period) -> path | None     non-blocking: the period's object can be loaded now
+      start_compile(period) -> Future  start (or join) the period's compile; result() = the path
+
+    wait: block on the compile (the behaviour before there was a choice). auto: jit when the
+    object is there, else start ONE compile for the period and answer generic until its future
+    is done; a compile that fails (or cannot start: no compiler) is logged once and the period
+    stays on generic, with no second attempt. off: always generic, never compiles."""
+
+    KEEP = 64  # periods remembered (paths, failures): a chain moves one period per 3 blocks
+
+    def __init__(self, mode: str, ready, start_compile):
+        if mode not in JIT_MODES:
+            raise ValueError(f"kawpow jit mode must be one of {', '.join(JIT_MODES)}, not {mode!r}")
+        self.mode = mode
+        self._ready = ready
+        self._start = start_compile
+        self._paths: dict[int, str] = {}
+        self._futs: dict[int, object] = {}
+        self._failed: dict[int, str] = {}
+
+    def pending(self, period: int):
+        """The compile future `period` is waiting on (auto), or None."""
+        return self._futs.get(period)
+
+    def _jit(self, period: int, path: str) -> KernelChoice:
+        self._paths[period] = path
+        while len(self._paths) > self.KEEP:
+            self._paths.pop(next(iter(self._paths)))
+        return KernelChoice("jit", path)
+
+    def _fail(self, period: int, err: BaseException) -> KernelChoice:
+        self._failed[period] = f"{type(err).__name__}: {err}"
+        while len(self._failed) > self.KEEP:
+            self._failed.pop(next(iter(self._failed)))
+        return KernelChoice("generic", None, f"kawpow: no compiled kernel for period {period} ({self._failed[period]}); "
+                                             "staying on the period-agnostic kernel")
+
+    def choose(self, period: int) -> KernelChoice:
+        path = self._paths.get(period)
+        if path is not None:
+            return KernelChoice("jit", path)
+        if self.mode == "off":
+            return KernelChoice("generic")
+        if self.mode == "wait":
+            try:
+                return self._jit(period, self._start(period).result())
+            except FileNotFoundError as e:  # no compiler on this machine
+                raise FileNotFoundError(f"{e}: the KawPow per-period kernel needs hipcc; {JIT_FLAG_HINT}") from e
+        if period in self._failed:
+            return KernelChoice("generic")
+        fut = self._futs.get(period)
+        if fut is None:
+            path = self._ready(period)
+            if path is not None:
+                return self._jit(period, path)
+            try:
+                fut = self._start(period)
+            except Exception as e:
+                return self._fail(period, e)
+            self._futs[period] = fut
+            while len(self._futs) > self.KEEP:  # periods the chain left before their compile ended
+                self._futs.pop(next(iter(self._futs)))
+        if not fut.done():
+            return KernelChoice("generic")
+        del self._futs[period]
+        err = fut.exception()
+        if err is not None:
+            return self._fail(period, err)
+        return self._jit(period, fut.result())
+
+
 def hipcc_available() -> bool:
     try:
         subprocess.run([os.path.join(_build.ROCM, "bin", "hipcc"), "--version"], capture_output=True, check=True)

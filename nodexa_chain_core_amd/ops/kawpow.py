@@ -5,7 +5,9 @@ generated program, see ops/jit.py). Reference behaviour: progpow::search /
 hash (src/crypto/ethash/lib/ethash/progpow.cpp:357-429, 567-579); unlike the
 reference's "first nonce wins" scan, one launch evaluates a whole nonce window
 and returns every share whose final hash passes the 64-bit target prefix; the
-host then re-checks each share bit-exactly (`Share.verify_host`).
+host then re-checks each share bit-exactly (`Share.verify_host`). While a period's kernel is not
+compiled yet the searcher can run the same window on the period-agnostic kernel
+(hip/kernels/kawpow_anyperiod.hip, the program as data) instead of waiting: `jit_mode`.
 
 Hashes here are in ethash storage order (the bytes progpow consumes); the
 node-level byte reversal of the SHA256d header hash lives in chain/header.py.
@@ -69,9 +71,17 @@ def target_prefix(boundary: bytes) -> int:
 
 
 class KawpowSearcher:
-    """Search / hash engine for one (device, epoch, period)."""
+    """Search / hash engine for one (device, epoch, period).
 
-    def __init__(self, epoch_dev: DeviceEpoch, block_number: int, prefetch_next: bool = False):
+    `jit_mode` (ops/jit.KernelChooser): "wait" blocks in `set_block` until the period's compiled
+    kernel exists; "auto" mines on the period-agnostic kernel (hip/kernels/kawpow_anyperiod.hip)
+    while the compile runs and swaps to the compiled one between two launches; "off" never
+    compiles. `kernel_kind` is the kernel the last launch used ("jit" / "generic")."""
+
+    PROGRAMS_RESIDENT = 8  # periods whose 256-byte program stays on the device
+
+    def __init__(self, epoch_dev: DeviceEpoch, block_number: int, prefetch_next: bool = False,
+                 jit_mode: str = "wait"):
         self.prefetch_next = prefetch_next
         self.epoch_dev = epoch_dev
         self.device = epoch_dev.device
@@ -80,6 +90,15 @@ class KawpowSearcher:
         self.period = -1
         self.kernel = None
         self.hash_kernel = None
+        self.jit_mode = jit_mode
+        self.defines = jit.defines_for(epoch_dev.dag_bytes)
+        self.granule = jit.granule_for(epoch_dev.dag_bytes)
+        self.chooser = jit.KernelChooser(jit_mode, lambda p: jit.ready(p, self.defines),
+                                         lambda p: jit.prefetch(p, self.defines))
+        self.kernel_kind = "jit" if jit_mode == "wait" else "generic"
+        self._kind = self.kernel_kind  # the kernel the next launch will use
+        self._programs: dict[int, torch.Tensor] = {}
+        self._any = self._any_hash = None
         self._scratch: torch.Tensor | None = None
         nbytes = self.h.sizeof_results()
         with torch.cuda.device(self.device):
@@ -92,21 +111,56 @@ class KawpowSearcher:
             raise ValueError(f"block {block_number} is not in epoch {self.epoch_dev.epoch}")
         period = block_number // 3
         if period != self.period:
-            defines = jit.defines_for(self.epoch_dev.dag_bytes)
-            with torch.cuda.device(self.device):
-                path = jit.get(period, defines)
-                co = runtime.load_code_object(path, key=path)
-                self.kernel = co.function("kawpow_search")
-                self.hash_kernel = co.function("kawpow_hash_batch")
+            self._choose(period)
             self.period = period
-            if self.prefetch_next:
-                jit.prefetch(period + 1, defines)  # next period compiles while this one mines
+            if self.prefetch_next and self.jit_mode != "off":
+                jit.prefetch(period + 1, self.defines)  # next period compiles while this one mines
+        elif self._kind == "generic" and self.jit_mode == "auto":
+            self._choose(period)  # swap to the compiled kernel once its compile is done
         self.block_number = block_number
+
+    def _choose(self, period: int) -> None:
+        """Ask the chooser which kernel this period runs on now; load what it names. Called from
+        `set_block` and at the top of `launch`, so a swap never happens inside a launch."""
+        c = self.chooser.choose(period)
+        if c.log:
+            from ..utils import log
+
+            log.log_printf(c.log)
+        with torch.cuda.device(self.device):
+            if c.kind == "jit":
+                co = runtime.load_code_object(c.path, key=c.path)
+                kernel = co.function("kawpow_search")
+                if self.jit_mode != "wait" and int(kernel.max_threads) != self.granule:
+                    raise RuntimeError(f"{c.path}: block {kernel.max_threads} is not the launch granule {self.granule}")
+                self.kernel, self.hash_kernel = kernel, co.function("kawpow_hash_batch")
+            else:
+                if self._any is None:
+                    self._any = runtime.static_kernel("kawpow_anyperiod", "kawpow_search_any")
+                    self._any_hash = runtime.static_kernel("kawpow_anyperiod", "kawpow_hash_any")
+                self._program(period)
+                self.kernel = self.hash_kernel = None  # an earlier period's compiled kernel is not this one's
+        self._kind = c.kind
+
+    def _program(self, period: int) -> torch.Tensor:
+        """The period's 64 program words on the device (uploaded once, the last few kept)."""
+        t = self._programs.get(period)
+        if t is None:
+            raw = _core.kawpow_programs_bytes([period])
+            assert len(raw) == 256
+            t = torch.frombuffer(bytearray(raw), dtype=torch.int32).to(self.device)
+            self._programs[period] = t
+            while len(self._programs) > self.PROGRAMS_RESIDENT:
+                self._programs.pop(next(iter(self._programs)))
+        return t
 
     @property
     def block(self) -> int:
-        """Threads per workgroup of the loaded variant = the nonce granularity of a launch."""
-        return int(self.kernel.max_threads)
+        """The nonce granularity of a launch: threads per workgroup of the compiled variant, which
+        the period-agnostic kernel covers per workgroup too (ops/jit.granule_for)."""
+        if self.jit_mode == "wait":
+            return int(self.kernel.max_threads)
+        return self.granule
 
     # ------------------------------------------------------------------
     def launch(self, header_hash: bytes, start_nonce: int, num_nonces: int, target64: int,
@@ -115,17 +169,26 @@ class KawpowSearcher:
         """Queue one search window on `stream` (no host sync). `results`: the share ring to append
         to (default: this searcher's own; the caller clears a ring it passes). `gen_word`: host-mapped
         generation word; workgroups that start after it moved past `generation` search nothing."""
+        if self._kind == "generic" and self.jit_mode == "auto":
+            self._choose(self.period)  # the compile may have finished since set_block
         if num_nonces % self.block:
             raise ValueError(f"num_nonces must be a multiple of {self.block}")
         with torch.cuda.device(self.device):
             s = runtime.current_stream_handle() if stream is None else stream
-            scratch = self.scratch(num_nonces)
             if results is None:
                 results = self.results
                 results[:4].zero_()
-            self.h.launch_kawpow_search(self.kernel, self.epoch_dev.dag.data_ptr(), self.epoch_dev.items2048,
-                                        results.data_ptr(), header_hash, start_nonce, target64, num_nonces, s,
-                                        scratch.data_ptr(), scratch.numel() * 4, gen_word, generation)
+            if self._kind == "generic":
+                self.h.launch_kawpow_search_any(self._any, self.epoch_dev.dag.data_ptr(), self.epoch_dev.items2048,
+                                                results.data_ptr(), header_hash, start_nonce, target64, num_nonces, s,
+                                                self._program(self.period).data_ptr(), self.epoch_dev.l1.data_ptr(),
+                                                self.granule, gen_word, generation)
+            else:
+                scratch = self.scratch(num_nonces)
+                self.h.launch_kawpow_search(self.kernel, self.epoch_dev.dag.data_ptr(), self.epoch_dev.items2048,
+                                            results.data_ptr(), header_hash, start_nonce, target64, num_nonces, s,
+                                            scratch.data_ptr(), scratch.numel() * 4, gen_word, generation)
+        self.kernel_kind = self._kind
 
     def scratch(self, num_nonces: int) -> torch.Tensor:
         """Per-nonce digest parking space (8 words/nonce) for the launch; grown on demand.
@@ -162,8 +225,14 @@ class KawpowSearcher:
         with torch.cuda.device(self.device):
             jobs = torch.frombuffer(buf, dtype=torch.uint8).to(self.device)
             out = torch.empty(n * 16, dtype=torch.int32, device=self.device)
-            self.h.launch_kawpow_hash_batch(self.hash_kernel, self.epoch_dev.dag.data_ptr(), self.epoch_dev.items2048,
-                                            jobs.data_ptr(), n, out.data_ptr(), runtime.current_stream_handle())
+            if self._kind == "generic":
+                self.h.launch_kawpow_hash_any(self._any_hash, self.epoch_dev.dag.data_ptr(), self.epoch_dev.items2048,
+                                              jobs.data_ptr(), n, out.data_ptr(), self._program(self.period).data_ptr(),
+                                              self.epoch_dev.l1.data_ptr(), runtime.current_stream_handle())
+            else:
+                self.h.launch_kawpow_hash_batch(self.hash_kernel, self.epoch_dev.dag.data_ptr(),
+                                                self.epoch_dev.items2048, jobs.data_ptr(), n, out.data_ptr(),
+                                                runtime.current_stream_handle())
             raw = out.cpu().numpy().tobytes()
         res = []
         for i in range(n):

@@ -9,6 +9,9 @@ network selection from -regtest / -testnet (SelectParams).
 
 New engine flags: -gpus=0,1,.. -kawpowactivationtime= -equihash
 -gpuintensity= -dagcache= -gpufailrate= -dropshare= -strictheight -dbformat=leveldb|journal
+-kawpowjit=wait|auto|off (default wait): what the KawPow GPU miner does while a ProgPoW period's
+compiled kernel does not exist yet: wait for the compile, mine on the period-agnostic kernel until
+it is there (auto), or never compile (off). Any other value is an init error.
 
 -maxconnections=<n>: maintain at most <n> connections to peers in total (default 125), as in the
 reference: up to min(8, n) of them outbound, and n less the outbound slots and one more for
@@ -21,6 +24,16 @@ import threading
 
 DEFAULT_CONF = "nodexa.conf"
 NETWORKS = ("main", "test", "regtest")
+KAWPOW_JIT_MODES = ("wait", "auto", "off")  # ops/jit.JIT_MODES (kept apart: no native import here)
+
+
+def kawpow_jit_mode(args: "ArgsManager") -> str:
+    """-kawpowjit=wait|auto|off, validated (ValueError with the init-error text otherwise)."""
+    mode = args.get("kawpowjit", "wait") or "wait"
+    if mode not in KAWPOW_JIT_MODES:
+        raise ValueError(f"Error: invalid -kawpowjit={mode} (expected {', '.join(KAWPOW_JIT_MODES[:-1])} "
+                         f"or {KAWPOW_JIT_MODES[-1]})")
+    return mode
 
 
 class ArgsManager:
