@@ -183,9 +183,36 @@ class RemoteMiner:
         return dict(self.stats)
 
 
+def _stratum_main(a) -> int:
+    """nodexa-miner -stratum=host:port [-stratum=...] -stratumuser= -stratumpass=: mine on a pool
+    (miner/stratum_client.py). No node RPC is used; -blocks=N stops after N accepted shares."""
+    from ..utils.config import kawpow_jit_mode
+    from .service import make_rank_device
+    from .stratum_client import StratumMiner, parse_endpoint
+
+    if a.is_set("minerrank"):
+        raise SystemExit("Error: -minerrank is not combined with -stratum: a pool gives every process "
+                         "(connection) an extranonce of its own, so the processes never overlap")
+    try:
+        endpoints = [parse_endpoint(e) for e in a.get_list("stratum")]
+        jit_mode = kawpow_jit_mode(a)
+    except ValueError as e:
+        raise SystemExit(f"Error: {e}" if not str(e).startswith("Error") else str(e))
+    cpu = a.get_bool("cpu", False)
+    backend = make_rank_device(cpu, None if cpu else a.get_int("gpu", 0), window=a.get_int("minerwindow", 4096),
+                               jit_mode=jit_mode)
+    m = StratumMiner(endpoints, backend, user=a.get("stratumuser", "") or "", password=a.get("stratumpass", "x") or "x",
+                     window=a.get_int("minerwindow", 1 << 25))
+    stats = m.run(max_shares=a.get_int("blocks", 0) or None)
+    print(stats)
+    # a share that went stale on its way is routine on a pool; any other rejection is this miner's fault
+    return 0 if stats["rejected"] == stats["rejected_stale"] and stats["bad_shares"] == 0 else 1
+
+
 def main(argv: list[str] | None = None) -> int:
     """nodexa-miner: -rpcconnect / -rpcport / -rpcuser / -rpcpassword of the node, -gpus=0,1..
-    (one process per GPU: pass -minerrank), -cpu for the host backend, -blocks=N to stop after N."""
+    (one process per GPU: pass -minerrank), -cpu for the host backend, -blocks=N to stop after N.
+    With -stratum=host:port it mines on a Stratum pool instead (_stratum_main)."""
     import sys
 
     from ..chain.state import make_params
@@ -194,6 +221,8 @@ def main(argv: list[str] | None = None) -> int:
 
     a = ArgsManager()
     a.parse_parameters(sys.argv[1:] if argv is None else argv)
+    if a.get_list("stratum"):
+        return _stratum_main(a)
     params = make_params(a.network)
     rpc = RPCClient(a.get("rpcconnect", "127.0.0.1"), a.get_int("rpcport", params.default_rpc_port),
                     a.get("rpcuser"), a.get("rpcpassword"), None, timeout=60.0)

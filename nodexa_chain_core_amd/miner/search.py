@@ -50,6 +50,9 @@ assert WORK_SIZE == 144
 FLAG_IDLE = 1    # nothing to mine: drain and wait for the next packet
 FLAG_STOP = 2    # leave the mining loop
 FLAG_CLEAN = 4   # the previous job is stale: abort its queued work
+# bits 8..15 of the flags: rank_shift s. Rank r owns [nonce_base + (r << s), nonce_base + ((r + 1) << s));
+# 0 (every packet without a pool-assigned nonce prefix) means 56 and an unbounded cursor, as ever
+RANK_SHIFT_LSB, RANK_SHIFT_MASK, RANK_SHIFT_DEFAULT = 8, 0xFF00, 56
 
 ALGO_KAWPOW, ALGO_EQUIHASH, ALGO_X16R, ALGO_X16RV2 = 0, 1, 2, 3
 ALGO_NAMES = ("kawpow", "equihash", "x16r", "x16rv2")
@@ -91,6 +94,15 @@ class Work:
     def stop(self) -> bool:
         return bool(self.flags & FLAG_STOP)
 
+    @property
+    def rank_shift(self) -> int:
+        return (self.flags & RANK_SHIFT_MASK) >> RANK_SHIFT_LSB or RANK_SHIFT_DEFAULT
+
+    @property
+    def rank_bounded(self) -> bool:
+        """The packet names its rank_shift: a rank's windows end where its range ends."""
+        return bool(self.flags & RANK_SHIFT_MASK)
+
     def pack(self) -> bytes:
         return struct.pack(WORK_FMT, self.header, self.boundary, self.height, self.algo, self.job_id,
                            self.nonce_base, self.flags)
@@ -107,6 +119,13 @@ class Work:
 
     def target(self) -> int:
         return int.from_bytes(self.boundary, "big")
+
+
+def rank_shift_flags(shift: int) -> int:
+    """The flag bits that carry rank_shift `shift` (1..64 - 1)."""
+    if not 0 < int(shift) < 64:
+        raise ValueError(f"rank_shift {shift} out of range")
+    return int(shift) << RANK_SHIFT_LSB
 
 
 def equihash_nonce256(nonce: int) -> bytes:
@@ -152,6 +171,7 @@ class SlotResult:
     algo: int = ALGO_KAWPOW
     end_ms: float = 0.0  # device clock: the window's end, ms after the device's first window began
     kernel: str = ""     # KawPow on a GPU: "jit" (per-period compiled kernel) or "generic" (period-agnostic)
+    dropped: int = 0     # hits the device found but its share ring had no room for
 
 
 class DeviceHung(RuntimeError):
@@ -344,11 +364,11 @@ class GpuSearchDevice:
         ev.synchronize()
         work, start, count, block, kind = self.meta[slot]
         self.meta[slot] = None
-        shares, _n, skipped = parse_results(self.host[slot].numpy().tobytes(), self.h.KAWPOW_MAX_SHARES)
+        shares, n, skipped = parse_results(self.host[slot].numpy().tobytes(), self.h.KAWPOW_MAX_SHARES)
         shares = [x for x in shares if _core.hash_le(x.final_hash, work.boundary)]
         hashes = max(0, count - skipped * block)
         return SlotResult(work.job_id, start, count, hashes, shares, self.starts[slot].elapsed_time(ev), skipped,
-                          ALGO_KAWPOW, self.anchor.elapsed_time(ev), kind)
+                          ALGO_KAWPOW, self.anchor.elapsed_time(ev), kind, max(0, n - self.h.KAWPOW_MAX_SHARES))
 
     def abort(self) -> None:
         """Make every queued or running window stale (its remaining workgroups exit at start)."""

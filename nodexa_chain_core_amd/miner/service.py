@@ -22,7 +22,12 @@ process group at all) and all ranks run the same step, `MiningService.step`:
 
 Nonce partition: rank r of n searches job-local windows from nonce_base + (r << 56) (X16R's 32-bit
 nNonce: r << 28), so ranks never overlap and a job change (new extranonce -> new header) restarts
-every cursor. DAGs are built sharded over the ranks and all-gathered (parallel/dag.py); the next
+every cursor. A packet that names a `rank_shift` s (bits 8..15 of its flags; a pool's nonce prefix,
+miner/stratum_client.py) gives rank r the range [nonce_base + (r << s), nonce_base + ((r + 1) << s))
+instead: a window is clipped to the range's end in whole launch granules, and a rank that has used
+its range up sends records without work (STATUS_EXHAUSTED) until the job changes; it never wraps
+into another rank's or another connection's range.
+DAGs are built sharded over the ranks and all-gathered (parallel/dag.py); the next
 epoch's DAG is prebuilt on a side stream once every rank reports its light cache ready (a vote in
 the gathered records, so the collective build starts on the same step everywhere). On RCCL the two
 collectives run from a high-priority stream with persistent pinned/device buffers, so they never
@@ -77,6 +82,7 @@ RECORD_PAYLOAD = max(MAX_SHARES[a] * s.size for a, s in _SHARE.items())  # 5536
 RECORD_SIZE = _REC_HEAD.size + RECORD_PAYLOAD                           # 5592
 STATUS_RESULT, STATUS_ALIVE, STATUS_VOTE = 1, 2, 4  # VOTE: next-epoch light cache ready
 STATUS_KERNEL_JIT, STATUS_KERNEL_GENERIC = 8, 16     # the KawPow kernel of the record's window (neither: not a GPU KawPow window)
+STATUS_EXHAUSTED = 32  # the rank has searched its whole nonce range of the current job (Work.rank_shift)
 _KERNEL_BITS = {"jit": STATUS_KERNEL_JIT, "generic": STATUS_KERNEL_GENERIC}
 
 
@@ -104,6 +110,8 @@ class RankRecord:
     alive: bool = True
     device: int = -1
     kernel: str = ""  # "jit" / "generic": the KawPow kernel of this window on a GPU rank
+    dropped: int = 0  # shares of this window lost to the device ring or to the record's share cap
+    exhausted: bool = False  # the rank's nonce range of the current job is used up
 
 
 def _as_record(r) -> RankRecord:
@@ -114,18 +122,22 @@ def _as_record(r) -> RankRecord:
 
 
 def pack_record(res: SlotResult | None, *, coll_ms: float = 0.0, failures: int = 0, epochs=(),
-                alive: bool = True, device: int = -1, vote: bool = False) -> bytes:
+                alive: bool = True, device: int = -1, vote: bool = False, exhausted: bool = False) -> bytes:
     out = bytearray(RECORD_SIZE)
     ep = sorted(epochs)
     lo, n = (ep[0], ep[-1] - ep[0] + 1) if ep else (0, 0)
     status = (STATUS_RESULT if res is not None else 0) | (STATUS_ALIVE if alive else 0) | (STATUS_VOTE if vote else 0)
+    status |= STATUS_EXHAUSTED if exhausted else 0
     if res is None:
         _REC_HEAD.pack_into(out, 0, 0, 0, 0, 0, 0, 0, int(coll_ms * 1e3), failures, lo, n, status, device)
         return bytes(out)
     status |= _KERNEL_BITS.get(getattr(res, "kernel", ""), 0)
     fmt = _SHARE[res.algo]
     shares = res.shares[:MAX_SHARES[res.algo]]
-    _REC_HEAD.pack_into(out, 0, res.job_id, res.hashes, len(shares), res.algo, min(int(res.device_ms * 1e3), 2**32 - 1),
+    # the share count is what the window found: the payload holds the first MAX_SHARES of them, and
+    # the reader counts the rest (and what the device ring had no room for) as dropped
+    found = min(len(res.shares) + getattr(res, "dropped", 0), 2**32 - 1)
+    _REC_HEAD.pack_into(out, 0, res.job_id, res.hashes, found, res.algo, min(int(res.device_ms * 1e3), 2**32 - 1),
                         res.aborted, min(int(coll_ms * 1e3), 2**32 - 1), failures, lo, n, status, device)
     for i, s in enumerate(shares):
         off = _REC_HEAD.size + i * fmt.size
@@ -165,7 +177,8 @@ def unpack_record(raw: bytes) -> RankRecord:
             shares.append(LegacyShare(*vals))
     return RankRecord(job, hashes, shares, algo, dev_us / 1e3, aborted, coll_us / 1e3, failures,
                       list(range(lo, lo + nep)), bool(status & STATUS_RESULT), bool(status & STATUS_ALIVE), device,
-                      "jit" if status & STATUS_KERNEL_JIT else "generic" if status & STATUS_KERNEL_GENERIC else "")
+                      "jit" if status & STATUS_KERNEL_JIT else "generic" if status & STATUS_KERNEL_GENERIC else "",
+                      n - len(shares), bool(status & STATUS_EXHAUSTED))
 
 
 class Comm:
@@ -381,6 +394,26 @@ def algo_for_time(params, t: int) -> int:
     return ALGO_X16RV2 if t >= params.x16rv2_activation_time else ALGO_X16R
 
 
+def solved_block(params, block, algo: int, sh):
+    """A copy of a job's template `block` with the share's proof of work in its header (the mining
+    loop's leader and the Stratum server build their blocks with it)."""
+    from ..chain.header import from_progpow
+
+    act = params.kawpow_activation_time
+    blk = _core.Block.deserialize(block.serialize(act), act)
+    hdr = blk.header
+    if algo == ALGO_KAWPOW:
+        hdr.nonce64 = sh.nonce
+        hdr.mix_hash = from_progpow(sh.mix_hash)
+    elif algo == ALGO_EQUIHASH:
+        hdr.nonce256 = sh.nonce256()
+        hdr.solution = sh.solution
+    else:
+        hdr.nonce = sh.nonce
+    blk.header = hdr
+    return blk
+
+
 class ChainLeader:
     """Rank 0's side of the loop: templates -> work packets, shares -> blocks.
 
@@ -532,21 +565,7 @@ class ChainLeader:
         return int.from_bytes(sh.block_hash, "little") <= int.from_bytes(job.boundary, "big")
 
     def _block_for(self, job: Job, sh):
-        from ..chain.header import from_progpow
-
-        act = self.state.params.kawpow_activation_time
-        blk = _core.Block.deserialize(job.block.serialize(act), act)
-        hdr = blk.header
-        if job.algo == ALGO_KAWPOW:
-            hdr.nonce64 = sh.nonce
-            hdr.mix_hash = from_progpow(sh.mix_hash)
-        elif job.algo == ALGO_EQUIHASH:
-            hdr.nonce256 = sh.nonce256()
-            hdr.solution = sh.solution
-        else:
-            hdr.nonce = sh.nonce
-        blk.header = hdr
-        return blk
+        return solved_block(self.state.params, job.block, job.algo, sh)
 
     def on_results(self, records) -> None:
         records = [_as_record(r) for r in records]
@@ -673,6 +692,13 @@ class MiningService:
         self.total_failures = 0
         self.dev_alive = True
         self.last_error = ""
+        self._tell_world_size()
+
+    def _tell_world_size(self) -> None:
+        """A leader that declares `world_size` learns the current one (at start, after a shrink): a
+        pool's nonce prefix is split over the ranks by it (miner/stratum_client.StratumLeader)."""
+        if self.leader is not None and hasattr(self.leader, "world_size"):
+            self.leader.world_size = self.world_size
 
     @property
     def rank(self) -> int:
@@ -706,7 +732,18 @@ class MiningService:
     def _window_start(self, w: Work) -> int:
         if w.algo in (ALGO_X16R, ALGO_X16RV2):
             return ((self.rank & 0xF) << 28) | (self.cursor & 0x0FFFFFFF)
-        return (w.nonce_base + (self.rank << 56) + self.cursor) & 0xFFFFFFFFFFFFFFFF
+        return (w.nonce_base + (self.rank << w.rank_shift) + self.cursor) & 0xFFFFFFFFFFFFFFFF
+
+    def _clip_window(self, w: Work, count: int) -> int:
+        """`count` clipped to the end of this rank's range of a packet that names its rank_shift, in
+        whole launch granules; 0 once the range is used up."""
+        if not w.rank_bounded or w.algo != ALGO_KAWPOW:
+            return count
+        left = (1 << w.rank_shift) - self.cursor
+        if count <= left:
+            return count
+        b = self.dev.block_for(w.height)
+        return max(0, left) // b * b
 
     def _device_failure(self, err: Exception) -> None:
         self.failures += 1
@@ -728,13 +765,17 @@ class MiningService:
         t0 = time.perf_counter()
         w = self.work
         res = None
+        exhausted = False
         try:
-            if w.idle or not self.dev_alive:
+            count = 0
+            if not w.idle and self.dev_alive:
+                count = self._clip_window(w, self.dev.window_for(w, self.window))
+                exhausted = count <= 0  # nothing of this job is left for this rank: no window, no wrap
+            if count <= 0:
                 res = self.pipe.drain() if self.pipe.inflight is not None else None
                 if res is None:
                     time.sleep(self.idle_sleep_s)
             else:
-                count = self.dev.window_for(w, self.window)
                 start = self._window_start(w)
                 if self.windows is not None:
                     self.windows.append((w.job_id, start, count))
@@ -748,7 +789,8 @@ class MiningService:
             res = None
         vote = self._next_epoch_vote()
         rec = pack_record(res, coll_ms=self.coll_ms, failures=self.failures, epochs=self.dev.resident_epochs(),
-                          alive=self.dev_alive, device=int(getattr(self.dev, "device", -1)), vote=bool(vote))
+                          alive=self.dev_alive, device=int(getattr(self.dev, "device", -1)), vote=bool(vote),
+                          exhausted=exhausted)
         tc = time.perf_counter()
         gathered = self.comm.all_gather(rec)
         coll = time.perf_counter() - tc
@@ -865,6 +907,7 @@ class MiningService:
         self.comm.abort()
         W.shrink(alive, timeout_s=int(max(1, self.collective_timeout_s)))
         self.comm.rebind()
+        self._tell_world_size()
         self.work = Work()
         self.cursor = 0
         self.repartitioned = True

@@ -77,6 +77,9 @@ class Node:
             self.mining_script = _core.address_to_script(addr, self.params.pubkey_prefix, self.params.script_prefix)
             if self.mining_script is None:
                 raise SystemExit(f"Error: invalid -miningaddress {addr} for {self.network}")
+        self.stratum = None
+        if args.is_set("stratumport") and self.mining_script is None:
+            raise SystemExit("Error: -stratumport needs -miningaddress (the reward script of the jobs it serves)")
 
     # ------------------------------------------------------------------ lifecycle
     def lock_datadir(self) -> None:
@@ -325,6 +328,8 @@ class Node:
         # the one miner: the mining service (miner/service.py) on every node — GPU ranks, or this
         # host's CPU devices — with -gpufailrate / -dropshare fault injection around its devices
         self.miner = Miner(self.state, self._start_miner_service(a))
+        if a.is_set("stratumport"):
+            self._start_stratum(a)
         self.metrics_writer = None
         if a.get("metricslog"):
             path = a.get("metricslog")
@@ -428,6 +433,24 @@ class Node:
                        f"{'cpu' if cpu else 'gpu'} devices, {window} nonces per window")
         return MS.MiningService(dev, leader, window=window, watchdog_s=float(a.get("minerwatchdog", "120")),
                                 collective_timeout_s=timeout, max_failures=a.get_int("minermaxfailures", 3)).start()
+
+    def _start_stratum(self, a: ArgsManager) -> None:
+        """-stratumport: the Stratum server (miner/stratum_server.py) on -stratumbind, jobs paying
+        -miningaddress, shares at -stratumsharebits, full share hashes on the miner's GPU when its
+        DAG is resident there."""
+        from .miner.stratum_server import ChainJobSource, StratumServer
+
+        source = ChainJobSource(self.state, self.mining_script, refresh_s=self.miner.leader.refresh_s)
+        self.stratum = StratumServer(source, host=a.get("stratumbind", "127.0.0.1"), port=a.get_int("stratumport", 0),
+                                     share_bits=a.get_int("stratumsharebits", 0), password=a.get("stratumpassword"),
+                                     max_connections=a.get_int("stratummaxconn", 64),
+                                     device=self.gpus[0] if self.gpus else None)
+        try:
+            self.stratum.start()
+        except OSError as e:
+            source.close()
+            self.stratum = None
+            raise SystemExit(f"Error: unable to bind the Stratum port: {e}")
 
     def params_assume_valid(self) -> str | None:
         """consensus.defaultAssumeValid: none is set for these networks here (the reference's main
@@ -760,6 +783,10 @@ class Node:
         if getattr(self, "_stopped", False):
             return
         self._stopped = True
+        if getattr(self, "stratum", None) is not None:  # before the chain state closes: its threads use it
+            self.stratum.stop()
+            self.stratum.source.close()
+            self.stratum = None
         if self.miner is not None:
             self.miner.close()
             if self.miner.service is not None:

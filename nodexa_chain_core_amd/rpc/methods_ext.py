@@ -764,3 +764,37 @@ def register(table, node) -> None:  # noqa: C901 — one table, like the referen
     table.append("util", "estimatefee", rpc_estimatefee, ("nblocks",))
     table.append("util", "estimatesmartfee", rpc_estimatesmartfee, ("conf_target", "estimate_mode"))
     table.append("hidden", "estimaterawfee", rpc_estimaterawfee, ("conf_target", "threshold"))
+
+    # ------------------------------------------------------------------ stratum
+    def rpc_getstratuminfo(p):
+        """getstratuminfo
+
+        The node's Stratum server (-stratumport; KawPow only).
+
+        Result:
+        {
+          "enabled": true|false,       (boolean) false without -stratumport; nothing else follows then
+          "port": n,                   (numeric) the listening port
+          "serving": true|false,       (boolean) a job is being served (false outside the KawPow era: "note" says why)
+          "algo": "kawpow",            (string) the proof of work of the next block
+          "height": n,                 (numeric) the height the current job mines
+          "job": {"id", "header_hash", "age"},   the current job (age in seconds)
+          "share_target": "hex",       (string) the effective share target: the easier of -stratumsharebits and the block target
+          "blocks_found": n,           (numeric) shares that met the block target and were accepted as blocks
+          "verified_gpu": n, "verified_host": n, "verify_batches_gpu": n, "verify_batches_host": n,
+                                       (numeric) shares fully hashed on the GPU's resident DAG / on the host, and the batches
+          "accepted": n, "rejected": n, ...      (numeric) server-wide counters
+          "connections": [             one entry per live connection
+            {"id", "address", "agent", "user", "extranonce", "connected" (seconds), "accepted",
+             "rejected" ({"code": n}), "last_share" (unix time), "hashrate" (accepted shares x 2^256 /
+             (share target + 1) over the connection's lifetime or the last 10 minutes, whichever is shorter)}
+          ],
+          "recent_connections": [...]  the last 8 closed connections as they ended, with "closed" (unix time)
+        }
+        """
+        srv = getattr(node, "stratum", None)
+        if srv is None:
+            return {"enabled": False}
+        return srv.info()
+
+    table.append("mining", "getstratuminfo", rpc_getstratuminfo, ())

@@ -16,6 +16,13 @@ it is there (auto), or never compile (off). Any other value is an init error.
 -maxconnections=<n>: maintain at most <n> connections to peers in total (default 125), as in the
 reference: up to min(8, n) of them outbound, and n less the outbound slots and one more for
 inbound peers; at that limit a new inbound peer takes the place of an evictable one or is refused.
+
+Stratum server of the node (miner/stratum_server.py; needs -miningaddress, KawPow only):
+-stratumport=<port> (off without it), -stratumbind=<addr> (default 127.0.0.1), -stratumsharebits=<n>
+(share target 2^(256-n) - 1 as -minertargetbits; the effective target is the easier of it and the
+block target), -stratumpassword=<pw> (mining.authorize must present it), -stratummaxconn=<n>
+(default 64; further connections are refused). nodexa-miner: -stratum=host:port (repeatable, tried
+in order), -stratumuser=, -stratumpass= (default x).
 """
 from __future__ import annotations
 
