@@ -50,6 +50,8 @@ assert WORK_SIZE == 144
 FLAG_IDLE = 1    # nothing to mine: drain and wait for the next packet
 FLAG_STOP = 2    # leave the mining loop
 FLAG_CLEAN = 4   # the previous job is stale: abort its queued work
+FLAG_REFORM = 8  # drain, then make the world again over the members named under the rendezvous store's
+#                  key "m<nonce_base>/members" (parallel/world.reform): a lost rank comes back
 # bits 8..15 of the flags: rank_shift s. Rank r owns [nonce_base + (r << s), nonce_base + ((r + 1) << s));
 # 0 (every packet without a pool-assigned nonce prefix) means 56 and an unbounded cursor, as ever
 RANK_SHIFT_LSB, RANK_SHIFT_MASK, RANK_SHIFT_DEFAULT = 8, 0xFF00, 56
@@ -182,12 +184,68 @@ class DeviceFault(RuntimeError):
     """A window failed on the device (a kernel error, a lost device, an injected fault)."""
 
 
+def dag_build_mode(resident_by_rank, pending_by_rank, epoch: int) -> str:
+    """How a rank that lacks `epoch`'s DAG builds it in a world that shares DAG builds.
+
+    "collective": sharded over the ranks and all-gathered; right only when every rank builds on the
+    same step, that is when no rank of the current world has the epoch resident or pending.
+    "solo": this rank builds the whole DAG alone, because a peer already holds the epoch or is
+    building it (a rank that joined late; its peers would never enter the all-gather).
+    `resident_by_rank` / `pending_by_rank`: per rank of the current world, the epochs it holds / is
+    building, as the last gathered records told (the same on every rank). None for the first: this
+    rank joined a running world and has seen no records yet; it assumes that its peers hold the
+    epoch."""
+    if resident_by_rank is None:
+        return "solo"
+    pending_by_rank = pending_by_rank or [()] * len(resident_by_rank)
+    for res, pend in zip(resident_by_rank, pending_by_rank):
+        if epoch in res or epoch in pend:
+            return "solo"
+    return "collective"
+
+
+class WorldEpochView:
+    """What one rank knows of the DAGs of every rank of its world: the epoch fields of the last
+    gathered records, and the epochs whose prebuild vote was unanimous (from that step on the epoch
+    is pending on every rank; all ranks see the same votes, so no wire field carries it)."""
+
+    def __init__(self, joined_late: bool = False):
+        self.joined_late = bool(joined_late)
+        self.resident: list | None = None
+        self.voted: set[int] = set()
+
+    def reset(self) -> None:
+        """The world was re-formed: the old records describe other ranks."""
+        self.resident = None
+        self.joined_late = True  # until the first records: whoever is in the new world may hold any epoch
+
+    def update(self, resident_by_rank) -> None:
+        self.resident = [set(r) for r in resident_by_rank]
+        self.voted = {e for e in self.voted if not all(e in r for r in self.resident)}
+
+    def vote_passed(self, epoch: int) -> None:
+        self.voted.add(int(epoch))
+
+    def mode(self, epoch: int, world_size: int) -> str:
+        if self.resident is None:
+            if self.joined_late:
+                return dag_build_mode(None, None, epoch)
+            resident = [set()] * world_size  # the start of the whole world: nobody holds anything
+        else:
+            resident = self.resident
+        return dag_build_mode(resident, [self.voted] * len(resident), epoch)
+
+
 class GpuSearchDevice:
     """One MI355X: resident epoch DAGs, per-period kernels, two share rings, the generation word.
 
     `collective_dag`: build DAGs sharded over the current process group and all-gather them
     (parallel/dag.py); every rank must then prepare the same epoch at the same step, which the
-    mining service guarantees (all ranks act on the same broadcast work packet).
+    mining service guarantees (all ranks act on the same broadcast work packet). A build is
+    collective only if no rank of the world has the epoch resident or pending (dag_build_mode, fed
+    by the service with every step's gathered records); otherwise, as on a rank that joined the
+    world late (`joined_late`), the rank that lacks the epoch builds the whole DAG alone.
+    `dag_build_mode[epoch]` records which it was, next to `dag_build_s[epoch]`.
 
     `jit_mode` (-kawpowjit, ops/kawpow.KawpowSearcher): "wait" stalls the loop in `submit` until a
     new period's kernel is compiled; "auto" runs such windows on the period-agnostic kernel and
@@ -196,7 +254,8 @@ class GpuSearchDevice:
     name = "gpu"
     MAX_EPOCHS = 2  # current + next (two 4 GiB DAGs are ~3 % of 288 GB)
 
-    def __init__(self, device: int = 0, collective_dag: bool = False, jit_mode: str = "wait"):
+    def __init__(self, device: int = 0, collective_dag: bool = False, jit_mode: str = "wait",
+                 joined_late: bool = False):
         import torch
 
         from ..ops import jit, runtime
@@ -214,6 +273,9 @@ class GpuSearchDevice:
         self.searchers: dict[int, object] = {}
         self.lock = threading.Lock()
         self.dag_build_s: dict[int, float] = {}
+        self.dag_build_mode: dict[int, str] = {}
+        self.dag_builds = 0  # DAG builds this device took part in
+        self.world_view = WorldEpochView(joined_late)
         nbytes = self.h.sizeof_results()
         with torch.cuda.device(self.device):
             # one stream per slot: the queued window starts on the CUs the running one's last
@@ -252,11 +314,14 @@ class GpuSearchDevice:
 
         torch = self.torch
         ws = W.get().world_size if self.collective_dag else 1
+        collective = self.collective_dag and self.world_view.mode(epoch, ws) == "collective"
+        self.dag_build_mode[epoch] = "collective" if collective else "solo"
+        self.dag_builds += 1
         t0 = time.perf_counter()
         with torch.cuda.device(self.device):
-            e = DeviceEpoch(epoch, device=self.device, world_size=ws)
+            e = DeviceEpoch(epoch, device=self.device, world_size=ws if collective else 1)
             with torch.cuda.stream(stream or self.stream):
-                if self.collective_dag:
+                if collective:
                     pdag.build_dag(e)
                 else:
                     e.build()
@@ -268,6 +333,9 @@ class GpuSearchDevice:
 
     def resident_epochs(self) -> list[int]:
         return sorted(self.epochs)
+
+    def pending_epochs(self) -> list[int]:
+        return sorted(self.pending_build)
 
     def prebuild(self, epoch: int) -> None:
         """Queue epoch's DAG build on the side stream (collective when sharded; every rank calls this
@@ -560,6 +628,14 @@ class RankDevice:
 
     def resident_epochs(self) -> list[int]:
         return self.kawpow.resident_epochs() if hasattr(self.kawpow, "resident_epochs") else []
+
+    def pending_epochs(self) -> list[int]:
+        return self.kawpow.pending_epochs() if hasattr(self.kawpow, "pending_epochs") else []
+
+    @property
+    def world_view(self):
+        """The KawPow device's view of its peers' DAGs (None: a device that shares no builds)."""
+        return getattr(self.kawpow, "world_view", None)
 
     def prebuild(self, epoch: int) -> None:
         self.kawpow.prebuild(epoch)

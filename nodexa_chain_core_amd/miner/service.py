@@ -42,6 +42,33 @@ Failure handling (the reference's miner just exits on errors, src/mi
   rendezvous store under a new membership epoch, wait out a grace period, rebuild the group over
   the ranks that registered (parallel/world.shrink) and carry on; rank 0 then issues a clean job
   so the nonce space is re-partitioned over the new ranks.
+* with -minerrejoin=<seconds> the lost rank comes back. A new process cannot enter an existing
+  torch.distributed default group, so such a world is made over a stand-alone rendezvous store that
+  rank 0 hosts (parallel/world.init(store_port=...)) and can be made again with other members
+  (parallel/world.reform). Rank 0 has initialised its GPU by then and must not start processes, so
+  the followers belong to a GPU-free supervisor that rank 0 starts before it touches a GPU
+  (miner/supervisor.py). The protocol is driven by rank 0 (Rejoiner), so no collective has to
+  fail first: the supervisor reports the exit (75 / 76 / a signal), the survivors shrink as above,
+  after the delay the supervisor starts a new process for that GPU, the newcomer prepares alone
+  (imports, its device, the light cache of the epoch rank 0 named), sets "join/<k>/ready/<id>" and
+  blocks on "m<k>/members"; rank 0 checks the ready key once per step without blocking, then names
+  the members and sets FLAG_REFORM in the next work packet; every rank drains, re-forms the world,
+  rebinds its communicator and resets cursor and work, rank 0 issues a clean job and the nonce
+  partition re-derives from (rank, world_size). The newcomer ends up in the same place: a
+  MiningService constructed after its world exists. Its first job's DAG it builds alone
+  (search.dag_build_mode), within one step, so the collective timeout must cover a DAG build (the
+  default 60 s does). A newcomer that dies before it is ready cancels the attempt (the survivors
+  never see FLAG_REFORM); one lost while the world is being re-formed makes the others re-form over
+  the members they were. A GPU that ends -minerrejoinmax times within -minerrejoinwindow seconds
+  stays evicted. The leader (id 0) is never replaced: its own device being evicted keeps today's
+  behaviour, it leads without searching. A torchrun world never re-joins (the launcher owns the
+  processes). getmininginfo.gpus[] keeps the entry of a rank that is out (state, lives, last_exit,
+  rejoin_in_s); counters miner_rejoins_total / miner_rejoin_failed_total / miner_rejoin_refused_total.
+Test hooks (environment only, never flags; the faults are the software ones of FaultInjectingDevice):
+NODEXA_MINER_FAIL_COLLECTIVE_AT=<n> makes the n-th collective of the loop raise;
+NODEXA_MINER_FAILRATE_LIVES=<n> applies the injected fail rate only while NODEXA_MINER_LIFE < n;
+NODEXA_MINER_FAILRATE_RANK=<id> applies it only to that rank; NODEXA_MINER_REFORM_AT=<step> makes
+rank 0 of a store world re-form the same membership once at that step.
 Resume: the leader persists {tip, extranonce} (miner_state.json); a restart on the same tip
 continues the extranonce sequence, so no template searched before the restart is searched again.
 """
@@ -62,7 +89,7 @@ import numpy as np
 from .. import core
 from ..utils import log
 from .search import (ALGO_EQUIHASH, ALGO_KAWPOW, ALGO_NAMES, ALGO_X16R, ALGO_X16RV2, EPOCH_PREBUILD_WINDOW,
-                     FLAG_CLEAN, FLAG_IDLE, FLAG_STOP, WORK_SIZE, DeviceFault, DeviceHung, EquihashShare,
+                     FLAG_CLEAN, FLAG_IDLE, FLAG_REFORM, FLAG_STOP, WORK_SIZE, DeviceFault, DeviceHung, EquihashShare,
                      LegacyShare, SearchPipeline, SlotResult, Work, as_rank_device)
 
 _core = core()
@@ -159,6 +186,21 @@ def record_totals(gathered: list[bytes]) -> tuple[int, int]:
         hashes += h
         votes += bool(status & STATUS_VOTE)
     return hashes, votes
+
+
+def record_epochs(gathered: list[bytes]) -> list[range]:
+    """Per rank, the epochs its record names (resident or being built)."""
+    out = []
+    for raw in gathered:
+        *_head, lo, n, _status, _dev = _REC_HEAD.unpack_from(raw, 0)
+        out.append(range(lo, lo + n))
+    return out
+
+
+def publish_members(store, k: int, members, membership: int) -> None:
+    """Rank 0 names the members of the next world under the store key "m<k>/members": the sorted
+    ids, the leader's first, and the membership number the new world gets (at least k)."""
+    store.set(f"m{k}/members", json.dumps({"members": [int(x) for x in members], "membership": int(membership)}))
 
 
 def unpack_record(raw: bytes) -> RankRecord:
@@ -442,6 +484,7 @@ class ChainLeader:
         self.stopping = False
         self.stats = {"shares": 0, "stale_shares": 0, "bad_shares": 0, "blocks": 0, "rejected": 0}
         self.per_rank: dict[int, dict] = {}
+        self.rank_ids: tuple = ()  # ids of the world's ranks (MiningService tells): per_rank is keyed by id
         self.state_path = state_path
         self._resume = self._load_state()
 
@@ -549,6 +592,7 @@ class ChainLeader:
         return Work(job.header, job.boundary, job.height, job.job_id, 0, FLAG_CLEAN, job.algo)
 
     def _rank_stats(self, r: int) -> dict:
+        r = self.rank_ids[r] if r < len(self.rank_ids) else r
         return self.per_rank.setdefault(r, {"shares": 0, "stale_shares": 0, "bad_shares": 0, "blocks": 0})
 
     def _check_share(self, job: Job, sh) -> bool:
@@ -657,7 +701,7 @@ class MiningService:
 
     def __init__(self, device, leader=None, *, window: int = 1 << 25, watchdog_s: float = 120.0,
                  collective_timeout_s: float = 60.0, grace_s: float | None = None, idle_sleep_s: float = 0.02,
-                 record_windows: bool = False, max_failures: int = 3):
+                 record_windows: bool = False, max_failures: int = 3, rejoin=None, membership: int = 0):
         from ..parallel import world as W
 
         self.W = W
@@ -674,12 +718,17 @@ class MiningService:
         self.cursor = 0
         self.rate = RateMeter()
         self.hashes_total = 0
+        self.own_hashes = 0                           # this rank's own work
+        self.first_result_at: float | None = None     # wall clock of this rank's first completed window
         self.rank_hashes: dict[int, int] = {}
         self.rank_info_raw: dict[int, dict] = {}
         self.kernel_windows = {"jit": 0, "generic": 0}  # GPU KawPow windows by kernel, all ranks (rank 0 only)
         self.rank_rates: dict[int, RateMeter] = {}
         self.steps = 0
-        self.membership = 0
+        self.membership = int(membership)  # a rank that joined late starts at the membership it joined
+        self.rejoin = rejoin               # rank 0 with -minerrejoin: the Rejoiner that brings lost ranks back
+        self.reforms = 0
+        self.reform_at = int(os.environ.get("NODEXA_MINER_REFORM_AT", "0"))  # test hook
         self.repartitioned = False
         self.windows: list[tuple[int, int, int]] | None = [] if record_windows else None
         self._light_thread: threading.Thread | None = None
@@ -699,6 +748,8 @@ class MiningService:
         pool's nonce prefix is split over the ranks by it (miner/stratum_client.StratumLeader)."""
         if self.leader is not None and hasattr(self.leader, "world_size"):
             self.leader.world_size = self.world_size
+        if self.leader is not None and hasattr(self.leader, "rank_ids"):
+            self.leader.rank_ids = self.member_ids
 
     @property
     def rank(self) -> int:
@@ -707,6 +758,11 @@ class MiningService:
     @property
     def world_size(self) -> int:
         return self.comm.w.world_size
+
+    @property
+    def member_ids(self) -> tuple:
+        """The id of every rank of the current world (its rank in the first world), by rank."""
+        return self.comm.w.member_ids
 
     def hashrate(self) -> float:
         return self.rate.rate()
@@ -784,11 +840,16 @@ class MiningService:
             if res is not None:
                 self.failures = 0
                 self.last_end_ms = res.end_ms
+                self.own_hashes += res.hashes
+                if self.first_result_at is None:
+                    self.first_result_at = time.time()
         except DeviceFault as e:
             self._device_failure(e)
             res = None
         vote = self._next_epoch_vote()
-        rec = pack_record(res, coll_ms=self.coll_ms, failures=self.failures, epochs=self.dev.resident_epochs(),
+        # resident or being built: what a peer needs to know to choose how it builds (search.dag_build_mode)
+        rec = pack_record(res, coll_ms=self.coll_ms, failures=self.failures,
+                          epochs=set(self.dev.resident_epochs()) | set(self.dev.pending_epochs()),
                           alive=self.dev_alive, device=int(getattr(self.dev, "device", -1)), vote=bool(vote),
                           exhausted=exhausted)
         tc = time.perf_counter()
@@ -797,15 +858,23 @@ class MiningService:
         hashes, votes = record_totals(gathered)
         self.hashes_total += hashes
         self.rate.add(hashes)
+        view = self.dev.world_view
+        if view is not None:
+            view.update(record_epochs(gathered))
         if vote and votes == self.world_size:
-            # every rank holds the light cache: all start the (collective) build on this step
+            # every rank holds the light cache: all start the build on this step (collective, unless
+            # a peer already holds that epoch: then the ranks that lack it build alone)
             self.dev.prebuild(w.epoch + 1)
             self._light_thread = None
+            if view is not None:
+                view.vote_passed(w.epoch + 1)
         payload = None
         if self.leader is not None:
             records = [unpack_record(r) for r in gathered]
             now = time.monotonic()
+            ids = self.member_ids
             for i, rec_i in enumerate(records):
+                i = ids[i]  # the counters follow the rank's id through a shrink and a re-join
                 self.rank_hashes[i] = self.rank_hashes.get(i, 0) + rec_i.hashes
                 self.rank_rates.setdefault(i, RateMeter()).add(rec_i.hashes, now)
                 info = self.rank_info_raw.setdefault(i, {"aborted": 0, "windows": 0, "jit_windows": 0,
@@ -823,8 +892,12 @@ class MiningService:
             self.leader.on_results(records)
             if self.world_size == 1 and not self.dev_alive and hasattr(self.leader, "fail"):
                 self.leader.fail("no mining device left (all evicted): " + self.last_error)
-            payload = self.leader.next_work(self.repartitioned).pack()
-            self.repartitioned = False
+            k = self._reform_due()
+            if k is not None:
+                payload = Work(nonce_base=k, flags=FLAG_IDLE | FLAG_REFORM).pack()
+            else:
+                payload = self.leader.next_work(self.repartitioned).pack()
+                self.repartitioned = False
         tc = time.perf_counter()
         new = Work.unpack(self.comm.broadcast(payload, WORK_SIZE))
         self.coll_ms = (coll + time.perf_counter() - tc) * 1e3
@@ -834,28 +907,95 @@ class MiningService:
             self.dev.abort()  # the window queued for the old job stops on the device
         self.work = new
         self.steps += 1
+        if new.flags & FLAG_REFORM:
+            self._reform(new.nonce_base)
         self.last_step_ms = (time.perf_counter() - t0) * 1e3
         return not new.stop
 
+    # ---------------------------------------------------------------- growing the world back
+    def _reform_due(self) -> int | None:
+        """Rank 0, once per step: the join attempt whose newcomer is ready (Rejoiner.poll), or the
+        NODEXA_MINER_REFORM_AT test hook (the same members again, once). Returns the number of the
+        store key that names the members, which goes out in a FLAG_REFORM packet."""
+        if self.reform_at and self.steps + 1 == self.reform_at and self.W.store() is not None:
+            k = max(self.membership, self.W.epoch()) + 1
+            publish_members(self.W.store(), k, self.member_ids, k)
+            return k
+        if self.rejoin is not None and not getattr(self.leader, "stopping", False):
+            return self.rejoin.poll(self)
+        return None
+
+    def _reform(self, k: int) -> None:
+        """Every rank, on the FLAG_REFORM packet: drain, make the world again over the members that
+        rank 0 published (parallel/world.reform) and start over as after a shrink: a new loop
+        communicator, a reset cursor, and rank 0 issues a clean job, so the nonce partition re-derives
+        from (rank, world_size). If the new world cannot be formed (a member died in between) the old
+        members form the next membership instead; a newcomer left outside ends itself."""
+        W = self.W
+        info = json.loads(W.store().get(f"m{k}/members"))
+        members, m = [int(x) for x in info["members"]], int(info["membership"])
+        old = list(self.member_ids)
+        try:
+            self.pipe.drain()
+        except DeviceHung:
+            raise
+        except Exception:  # noqa: BLE001 — the window of the old world is discarded
+            self.pipe.inflight = None
+        timeout = int(max(5.0, self.collective_timeout_s))
+        try:
+            W.reform(members, m, timeout_s=timeout)
+        except Exception as e:  # noqa: BLE001 — a member was lost while the world was being made
+            log.log_printf(f"miner rank id {old[self.rank] if self.rank < len(old) else '?'}: re-forming over "
+                           f"{members} failed ({e}); the ranks {old} continue")
+            m += 1
+            W.reform(old, m, timeout_s=timeout)
+            if self.rejoin is not None:
+                self.rejoin.reform_failed()
+        else:
+            if self.rejoin is not None:
+                self.rejoin.reformed(members)
+        self.comm.rebind()
+        self.membership = m
+        self.reforms += 1
+        if self.dev.world_view is not None:
+            self.dev.world_view.reset()
+        self._tell_world_size()
+        self.work = Work()
+        self.cursor = 0
+        self.repartitioned = True
+        log.log_printf(f"miner: membership {m}: rank {self.rank} of {self.world_size} (ids {list(self.member_ids)})")
+
     # ---------------------------------------------------------------- observability
     def rank_info(self) -> list[dict]:
-        """getmininginfo.gpus[]: one entry per rank of the world (rank 0 only)."""
+        """getmininginfo.gpus[]: one entry per rank of the world (rank 0 only). With -minerrejoin a
+        rank that is out keeps its entry (rank -1, its counters as they stood); `state` is mining /
+        evicted / rejoining / refused, `lives` the processes started for it so far, `last_exit` the
+        exit code of the last one that ended, `rejoin_in_s` the time until it may be spawned again."""
         out = []
         stats = getattr(self.leader, "per_rank", {}) if self.leader is not None else {}
-        for r in range(self.world_size):
-            info = self.rank_info_raw.get(r, {})
-            rs = stats.get(r, {})
+        ids = list(self.member_ids)
+        away = [g for g in (self.rejoin.known_ids() if self.rejoin is not None else []) if g not in ids]
+        for r, gid in [(r, g) for r, g in enumerate(ids)] + [(-1, g) for g in away]:
+            info = self.rank_info_raw.get(gid, {})
+            rs = stats.get(gid, {})
             algo = info.get("algo", self.work.algo)
             shares, stale = rs.get("shares", 0), rs.get("stale_shares", 0)
-            rate = self.rank_rates[r].rate() if r in self.rank_rates else 0.0
+            rate = self.rank_rates[gid].rate() if gid in self.rank_rates and r >= 0 else 0.0
+            life = self.rejoin.describe(gid) if self.rejoin is not None else {}
             out.append({
                 "rank": r,
+                "id": gid,
+                "state": life.get("state", "mining" if (info.get("alive", True) if gid else self.dev_alive)
+                                  else "evicted"),
+                "lives": life.get("lives", 1),
+                "last_exit": life.get("last_exit"),
+                "rejoin_in_s": life.get("rejoin_in_s"),
                 "device": info.get("device", -1),
-                "alive": info.get("alive", True) if r else self.dev_alive,
+                "alive": (info.get("alive", True) if gid else self.dev_alive) and r >= 0,
                 "algo": ALGO_NAMES[algo] if algo < len(ALGO_NAMES) else str(algo),
                 ("solutionspersec" if algo == ALGO_EQUIHASH else "hashespersec"): round(rate, 1),
                 "mhs": round(rate / 1e6, 3) if algo != ALGO_EQUIHASH else None,
-                "hashes": int(self.rank_hashes.get(r, 0)),
+                "hashes": int(self.rank_hashes.get(gid, 0)),
                 "shares": shares,
                 "stale_shares": stale,
                 "stale_rate": round(stale / shares, 4) if shares else 0.0,
@@ -905,7 +1045,12 @@ class MiningService:
         except Exception:  # noqa: BLE001 — the window of the broken step is discarded
             pass
         self.comm.abort()
-        W.shrink(alive, timeout_s=int(max(1, self.collective_timeout_s)))
+        # the survivors arrive here up to one collective timeout apart (a rank next to the lost one
+        # sees its socket close at once, the others wait their collective out), so the new group's
+        # connect gets the grace period (gloo connects its full mesh under the group's timeout; every
+        # collective on it stays bounded by Comm's own). RCCL connects lazily and keeps the timeout.
+        conn = self.collective_timeout_s if w.backend == "nccl" else max(self.collective_timeout_s, self.grace_s)
+        W.shrink(alive, timeout_s=int(max(1, conn)))
         self.comm.rebind()
         self._tell_world_size()
         self.work = Work()
@@ -952,6 +1097,192 @@ class MiningService:
         self._stop.set()
         self._thread.join(timeout)
         self._thread = None
+
+
+class Rejoiner:
+    """Rank 0's side of a lost rank's return (-minerrejoin), driven from the loop so that no
+    collective has to fail first. `poll` runs once per step:
+
+      * the supervisor reported that a member's process ended (75 hung, 76 evicted, a signal): the
+        rank is `evicted`; the survivors shrink on their own (MiningService.recover);
+      * once the world no longer holds the rank and RejoinPolicy says "spawn", the supervisor starts
+        a new process for it with join_membership k; one attempt at a time. The newcomer prepares
+        alone (imports, its device, the light cache of the epoch under "join/<k>/epoch"), sets
+        "join/<k>/ready/<id>" and blocks on "m<k>/members";
+      * when the ready key is there (a non-blocking check), rank 0 publishes the members and `poll`
+        returns k: the next work packet carries FLAG_REFORM and every rank re-forms the world;
+      * a newcomer whose exit is reported before it was ready cancels the attempt, which counts as
+        a life and as a failed re-join; the survivors never see FLAG_REFORM for it.
+
+    The leader, id 0, is never replaced: when its own device is evicted it keeps leading without
+    searching, as without -minerrejoin."""
+
+    def __init__(self, supervisor, policy, *, gpus: list[int], env: dict, argv: list | None = None):
+        from ..utils.metrics import REGISTRY
+
+        self.sup = supervisor
+        self.policy = policy
+        self.gpus = list(gpus)          # id -> device index
+        self.env = dict(env)            # what every follower gets (follower_env, the ports)
+        self.argv = argv                # test hook: another program in place of the follower
+        self.ranks = {g: {"state": "mining", "lives": 1, "last_exit": None} for g in range(len(self.gpus))}
+        self.attempt: dict | None = None
+        self.last_k = 0
+        self.counters = {"miner_rejoins_total": 0, "miner_rejoin_failed_total": 0, "miner_rejoin_refused_total": 0}
+        self.metrics = REGISTRY
+        self.last_event: dict = {}      # id -> wall clock of its last `exited` event (measurements)
+        self.exit_log: list[dict] = []  # every `exited` event, in order
+        self.lock = threading.Lock()
+
+    def spawn_first(self) -> None:
+        """The followers of the first world, life 0."""
+        for g in range(1, len(self.gpus)):
+            self.sup.spawn(gpu=self.gpus[g], rank=g, world_size=len(self.gpus), env=self.env)
+
+    def known_ids(self) -> list[int]:
+        return sorted(self.ranks)
+
+    def describe(self, g: int) -> dict:
+        with self.lock:
+            d = dict(self.ranks.get(g, {}))
+        if d.get("state") == "evicted":
+            t = self.policy.rejoin_in(self.policy.clock(), g)
+            d["rejoin_in_s"] = None if t is None else round(t, 3)
+        return d
+
+    def _count(self, name: str) -> None:
+        self.counters[name] += 1
+        self.metrics.inc(name, 1, worker="service")
+
+    def _exited(self, ev: dict) -> None:
+        g, code = int(ev["rank"]), int(ev["code"])
+        self.exit_log.append(ev)
+        st = self.ranks.get(g)
+        if st is None or code == 0:
+            return
+        self.last_event[g] = time.time()
+        self.policy.record_exit(g)
+        with self.lock:
+            st["last_exit"] = code
+            st["state"] = "evicted"
+        if self.attempt is not None and self.attempt["id"] == g:
+            self.attempt = None
+            self._count("miner_rejoin_failed_total")
+            log.log_printf(f"miner: rank id {g} ended with {code} before it was ready; the re-join is cancelled")
+        else:
+            log.log_printf(f"miner: rank id {g} ended with {code} (life {ev.get('life')})")
+
+    def poll(self, svc: "MiningService") -> int | None:
+        for ev in self.sup.events():
+            if ev.get("event") == "exited":
+                self._exited(ev)
+            elif ev.get("event") == "error":
+                log.log_printf(f"miner supervisor: {ev.get('error')}")
+                a = self.attempt
+                if a is not None and not a.get("published"):
+                    # the spawn was not carried out (the last process of that rank has not ended yet):
+                    # the attempt is over, and the policy's delay applies before the next one
+                    self.attempt = None
+                    with self.lock:
+                        self.ranks[a["id"]]["state"] = "evicted"
+                        self.ranks[a["id"]]["lives"] -= 1
+                    self.policy.record_exit(a["id"])
+                    self._count("miner_rejoin_failed_total")
+        store = svc.W.store()
+        if store is None:
+            return None
+        members = list(svc.member_ids)
+        if self.attempt is not None:
+            a = self.attempt
+            if a.get("published") or not store.check([f"join/{a['k']}/ready/{a['id']}"]):
+                return None
+            m = max(a["k"], svc.membership + 1)
+            publish_members(store, a["k"], sorted(set(members) | {a["id"]}), m)
+            a["published"] = True
+            return a["k"]
+        now = self.policy.clock()
+        for g, st in sorted(self.ranks.items()):
+            if g == 0 or st["state"] not in ("evicted", "refused") or g in members:
+                continue  # (still a member: the survivors have not shrunk yet)
+            what = self.policy.decide(now, g)
+            if what == "refused":
+                if st["state"] == "refused":
+                    continue  # said once; it becomes eligible again when its exits leave the window
+                with self.lock:
+                    st["state"] = "refused"
+                self._count("miner_rejoin_refused_total")
+                log.log_printf(f"miner: rank id {g} (gpu {self.gpus[g]}) stays evicted: {self.policy.recent_exits(now, g)} "
+                               f"exits within {self.policy.window_s:.0f} s (-minerrejoinmax={self.policy.max_exits})")
+            elif what == "spawn":
+                k = self.last_k = max(self.last_k, svc.membership, svc.W.epoch()) + 1  # never a key used before
+                w = svc.work
+                store.set(f"join/{k}/epoch", str(w.epoch if not w.idle and w.algo == ALGO_KAWPOW else -1))
+                self.sup.spawn(gpu=self.gpus[g], rank=g, world_size=len(members) + 1, env=self.env,
+                               join_membership=k, argv=self.argv)
+                with self.lock:
+                    st["state"] = "rejoining"
+                    st["lives"] += 1
+                self.attempt = {"id": g, "k": k}
+                log.log_printf(f"miner: starting life {st['lives'] - 1} of rank id {g} (gpu {self.gpus[g]}), "
+                               f"join membership {k}")
+                break
+        return None
+
+    def reformed(self, members: list[int]) -> None:
+        a, self.attempt = self.attempt, None
+        if a is not None and a["id"] in members:
+            with self.lock:
+                self.ranks[a["id"]]["state"] = "mining"
+            self._count("miner_rejoins_total")
+
+    def reform_failed(self) -> None:
+        """The world with the newcomer could not be formed; its exit event will follow and count
+        against it (RejoinPolicy)."""
+        a, self.attempt = self.attempt, None
+        if a is not None:
+            with self.lock:
+                self.ranks[a["id"]]["state"] = "evicted"
+            self._count("miner_rejoin_failed_total")
+
+    def wait_followers(self, timeout: float = 30.0) -> None:
+        """After the stop packet: until every follower has ended by itself (their exits are logged)."""
+        deadline = time.monotonic() + timeout
+        while time.monotonic() < deadline:
+            for ev in self.sup.events():
+                if ev.get("event") == "exited":
+                    self.exit_log.append(ev)
+            try:
+                if not self.sup.status()["children"]:
+                    break
+            except Exception:  # noqa: BLE001 — the supervisor is gone, and its followers with it
+                break
+            time.sleep(0.05)
+        for ev in self.sup.events():
+            if ev.get("event") == "exited":
+                self.exit_log.append(ev)
+
+    def close(self) -> None:
+        self.sup.stop()
+
+
+def start_rejoin_world(gpus: list[int], port: int, *, cpu: bool, env: dict, policy, argv: list | None = None):
+    """What rank 0 does in place of spawn_followers when lost ranks are to come back: start the
+    supervisor (before this process touches a GPU), have it start ranks 1..n-1, and return the
+    Rejoiner for MiningService(rejoin=...) and the port of the stand-alone rendezvous store for
+    parallel/world.init(store_port=...). `port`: the env:// port the followers are told anyway."""
+    import socket
+
+    from . import supervisor as SV
+
+    with socket.socket() as sk:
+        sk.bind(("127.0.0.1", 0))
+        store_port = sk.getsockname()[1]
+    full = dict(env)
+    full.update({"MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(port), "NODEXA_MINER_CPU": "1" if cpu else "0",
+                 "NODEXA_MINER_STORE_PORT": str(store_port), "PYTHONPATH": SV.follower_pythonpath()})
+    rj = Rejoiner(SV.SupervisorClient(), policy, gpus=gpus, env=full, argv=argv)
+    rj.spawn_first()
+    return rj, store_port
 
 
 class Miner:
@@ -1092,11 +1423,26 @@ def follower_jit_mode() -> str:
     return mode
 
 
+def injected_fail_rate(rate: float, rank_id: int) -> float:
+    """-gpufailrate as it applies to this process. Two test hooks (environment only) narrow it:
+    NODEXA_MINER_FAILRATE_RANK=<id>: only the rank with that id fails; NODEXA_MINER_FAILRATE_LIVES=<n>:
+    only while NODEXA_MINER_LIFE < n, so a re-spawned rank comes back healthy. The faults are the
+    software ones of search.FaultInjectingDevice."""
+    only = os.environ.get("NODEXA_MINER_FAILRATE_RANK")
+    if only not in (None, "") and int(only) != int(rank_id):
+        return 0.0
+    lives = os.environ.get("NODEXA_MINER_FAILRATE_LIVES")
+    if lives not in (None, "") and int(os.environ.get("NODEXA_MINER_LIFE", "0")) >= int(lives):
+        return 0.0
+    return float(rate)
+
+
 def make_rank_device(cpu: bool, device_index: int | None = None, collective_dag: bool = False, window: int = 4096,
                      fail_rate: float = 0.0, drop_rate: float = 0.0, seed: int = 0, eq_window: int = 1,
-                     jit_mode: str = "wait"):
+                     jit_mode: str = "wait", joined_late: bool = False):
     """This rank's RankDevice: GPU KawPow + GPU Equihash (built on first use) + GPU X16R, or the
-    host equivalents; -gpufailrate / -dropshare wrap it."""
+    host equivalents; -gpufailrate / -dropshare wrap it. `joined_late`: the rank enters a running
+    world, whose DAGs it builds alone (search.dag_build_mode)."""
     from .equihash_search import EquihashCpuDevice
     from .search import CpuSearchDevice, FaultInjectingDevice, RankDevice
 
@@ -1107,11 +1453,44 @@ def make_rank_device(cpu: bool, device_index: int | None = None, collective_dag:
         from .search import GpuSearchDevice, LegacyGpuDevice
 
         idx = int(device_index or 0)
-        dev = RankDevice(GpuSearchDevice(idx, collective_dag=collective_dag, jit_mode=jit_mode),
-                         equihash_factory=lambda: EquihashGpuDevice(idx), legacy=LegacyGpuDevice(idx))
+        kawpow = GpuSearchDevice(idx, collective_dag=collective_dag, jit_mode=jit_mode)
+        if joined_late:
+            kawpow.world_view.joined_late = True
+        dev = RankDevice(kawpow, equihash_factory=lambda: EquihashGpuDevice(idx), legacy=LegacyGpuDevice(idx))
     if fail_rate or drop_rate:
         dev = FaultInjectingDevice(dev, fail_rate, drop_rate, seed=seed)
     return dev
+
+
+def join_world(k: int, my_id: int, store_port: int, *, cpu: bool, device_index: int | None):
+    """A re-spawned rank before it has a world (join attempt `k`): open the device, build what needs
+    no peer (the light cache of the epoch rank 0 named under "join/<k>/epoch"), set
+    "join/<k>/ready/<id>" and block on "m<k>/members" under the rendezvous timeout. Returns
+    (member ids, membership), or None when nobody named the members in time."""
+    import datetime as dt
+
+    from ..parallel import world as W
+
+    if not cpu:
+        import torch
+
+        torch.cuda.set_device(int(device_index or 0))
+        torch.cuda.current_stream().synchronize()  # the device is open before this rank says "ready"
+    store = W.connect_store(store_port)
+    try:
+        epoch = int(store.get(f"join/{k}/epoch"))
+    except Exception:  # noqa: BLE001 — nothing named: nothing to prepare
+        epoch = -1
+    if epoch >= 0:
+        _core.get_epoch_context(epoch)
+    store.set(f"join/{k}/ready/{my_id}", "1")
+    try:
+        store.wait([f"m{k}/members"], dt.timedelta(seconds=W.rendezvous_timeout()))
+    except Exception as e:  # noqa: BLE001 — the store's timeout error
+        log.log_printf(f"miner rank id {my_id}: not named a member of membership {k} in time ({e})")
+        return None
+    info = json.loads(store.get(f"m{k}/members"))
+    return [int(x) for x in info["members"]], int(info["membership"])
 
 
 def follower_main() -> int:
@@ -1123,28 +1502,55 @@ def follower_main() -> int:
     timeout = float(os.environ.get("NODEXA_MINER_COLLECTIVE_TIMEOUT", "60"))
     watchdog = float(os.environ.get("NODEXA_MINER_WATCHDOG", "120"))
     window = int(os.environ.get("NODEXA_MINER_WINDOW", str(1 << 25)))
-    W.init(use_gpu=not cpu, device_index=None if dev_index is None else int(dev_index),
-           timeout_s=max(int(timeout), W.rendezvous_timeout()), elastic=True, collective_timeout_s=timeout)
+    store_port = os.environ.get("NODEXA_MINER_STORE_PORT")
+    join = os.environ.get("NODEXA_MINER_JOIN_MEMBERSHIP")
+    life = int(os.environ.get("NODEXA_MINER_LIFE", "0"))
+    my_id = int(os.environ.get("RANK", "0"))
+    kw = {"use_gpu": not cpu, "device_index": None if dev_index is None else int(dev_index),
+          "timeout_s": max(int(timeout), W.rendezvous_timeout()), "elastic": True, "collective_timeout_s": timeout,
+          "store_port": None if store_port is None else int(store_port)}
+    membership = 0
+    if join is not None:
+        # a re-spawned rank: prepare alone, say so, and wait to be named a member of the next world
+        if store_port is None:
+            raise SystemExit("NODEXA_MINER_JOIN_MEMBERSHIP needs NODEXA_MINER_STORE_PORT")
+        info = join_world(int(join), my_id, int(store_port), cpu=cpu, device_index=kw["device_index"])
+        if info is None:
+            return 4
+        members, membership = info
+        kw.update(rank=members.index(my_id), world_size=len(members), membership=membership, ids=members,
+                  timeout_s=int(max(5.0, timeout)))
+    W.init(**kw)
     w = W.get()
     dev = make_rank_device(cpu, w.device.index if not cpu else None, collective_dag=w.collective, window=window,
-                           fail_rate=float(os.environ.get("NODEXA_MINER_FAILRATE", "0") or 0),
-                           drop_rate=float(os.environ.get("NODEXA_MINER_DROPSHARE", "0") or 0), seed=w.rank,
-                           jit_mode=follower_jit_mode())
+                           fail_rate=injected_fail_rate(float(os.environ.get("NODEXA_MINER_FAILRATE", "0") or 0), my_id),
+                           drop_rate=float(os.environ.get("NODEXA_MINER_DROPSHARE", "0") or 0), seed=my_id,
+                           jit_mode=follower_jit_mode(), joined_late=join is not None)
     hang = int(os.environ.get("NODEXA_MINER_HANG_AFTER", "0"))
     if hang > 0:  # fault injection for the failure-handling tests
         from .search import HangingDevice
 
         dev = HangingDevice(dev, hang)
     wlog = os.environ.get("NODEXA_MINER_WINDOWS_LOG")
+    if wlog:
+        # "{id}" in the path: one environment serves a whole supervised world; every life of a rank
+        # writes a log of its own
+        wlog = wlog.replace("{id}", str(my_id)) + (f".life{life}" if life else "")
     svc = MiningService(dev, None, window=window, watchdog_s=watchdog, collective_timeout_s=timeout,
-                        record_windows=bool(wlog), max_failures=int(os.environ.get("NODEXA_MINER_MAXFAILURES", "3")))
+                        record_windows=bool(wlog), max_failures=int(os.environ.get("NODEXA_MINER_MAXFAILURES", "3")),
+                        membership=membership)
 
     def dump():
         if wlog:
+            kd = getattr(svc.dev, "kawpow", None)
             with open(wlog, "w") as f:
                 json.dump({"rank": svc.rank, "world_size": svc.world_size, "windows": svc.windows,
                            "steps": svc.steps, "hashes_total": svc.hashes_total,
-                           "failures": svc.total_failures}, f)
+                           "failures": svc.total_failures, "id": my_id, "life": life, "reforms": svc.reforms,
+                           "membership": svc.membership, "own_hashes": svc.own_hashes,
+                           "first_window_at": svc.first_result_at,
+                           "dag_build_mode": {str(k): v for k, v in getattr(kd, "dag_build_mode", {}).items()},
+                           "dag_build_s": {str(k): v for k, v in getattr(kd, "dag_build_s", {}).items()}}, f)
 
     try:
         svc.run()

@@ -35,7 +35,7 @@ from .rpc import (methods, methods_assets, methods_ext, methods_index, methods_m
                   methods_wallet_ext)
 from .rpc.server import RPCServer, RPCTable, delete_cookie, make_cookie
 from .utils import log, metrics
-from .utils.config import ArgsManager, gpu_list, kawpow_jit_mode
+from .utils.config import ArgsManager, gpu_list, kawpow_jit_mode, miner_rejoin_args
 
 _core = core()
 
@@ -388,7 +388,11 @@ class Node:
         Ranks 1..n-1 are spawned as child processes here, before this process touches a GPU; under
         torchrun (WORLD_SIZE > 1 in the environment) the launcher made them and this is its rank 0.
         Without GPUs the same loop runs on this host's CPU devices: one rank and no process group,
-        or `-minerservice -minerranks=N` processes over gloo (rehearsals of the multi-GPU path)."""
+        or `-minerservice -minerranks=N` processes over gloo (rehearsals of the multi-GPU path).
+        With `-minerrejoin=<seconds>` the followers belong to a GPU-free supervisor (miner/supervisor.py)
+        that this process starts here, still before it touches a GPU, and a rank that was evicted or
+        hung is started again after that delay and taken back into the world (miner/service.Rejoiner);
+        `-minerrejoinmax` exits within `-minerrejoinwindow` seconds leave it evicted."""
         from .miner import service as MS
         from .parallel import world as W
 
@@ -400,8 +404,15 @@ class Node:
         timeout = float(a.get("minercollectivetimeout", "60"))
         fail, drop = float(a.get("gpufailrate", "0") or 0), float(a.get("dropshare", "0") or 0)
         self.miner_procs = []
+        try:
+            rejoin_s, rejoin_max, rejoin_window = miner_rejoin_args(a)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        rejoiner, store_port = None, None
         ranks = max(1, a.get_int("minerranks", 1)) if a.get_bool("minerservice", False) else 1
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            if rejoin_s > 0:
+                log.log_printf("miner service: -minerrejoin is ignored in a torchrun world (the launcher owns the ranks)")
             W.init(use_gpu=not cpu, timeout_s=max(int(timeout), W.rendezvous_timeout()), elastic=True,
                    collective_timeout_s=timeout)
         elif cpu and ranks == 1 and not a.get_bool("minerforcecollectives", False):
@@ -418,21 +429,29 @@ class Node:
                 env = MS.follower_env(timeout=timeout, watchdog=a.get("minerwatchdog", "120"),
                                       max_failures=a.get_int("minermaxfailures", 3), fail_rate=fail, drop_rate=drop,
                                       jit_mode=jit_mode, window=a.get("gpuintensity"))
-                self.miner_procs = MS.spawn_followers(gpus, port, cpu=cpu, extra_env=env)
+                if rejoin_s > 0:
+                    from .miner.supervisor import RejoinPolicy
+
+                    policy = RejoinPolicy(rejoin_s, rejoin_max, rejoin_window)
+                    rejoiner, store_port = MS.start_rejoin_world(gpus, port, cpu=cpu, env=env, policy=policy)
+                    self.miner_rejoiner = rejoiner
+                else:
+                    self.miner_procs = MS.spawn_followers(gpus, port, cpu=cpu, extra_env=env)
             W.init(use_gpu=not cpu, timeout_s=max(int(timeout), W.rendezvous_timeout()),
-                   device_index=None if cpu else gpus[0],
+                   device_index=None if cpu else gpus[0], store_port=store_port,
                    rank=0, world_size=len(gpus), elastic=True, collective_timeout_s=timeout,
                    force_collectives=a.get_bool("minerforcecollectives", False) or None)
         w = W.get()
         window = a.get_int("gpuintensity", 4096 if cpu else 1 << 25)
         dev = MS.make_rank_device(cpu, None if cpu else w.device.index, collective_dag=w.collective, window=window,
-                                  fail_rate=fail, drop_rate=drop, seed=0, jit_mode=jit_mode)
+                                  fail_rate=MS.injected_fail_rate(fail, 0), drop_rate=drop, seed=0, jit_mode=jit_mode)
         leader = MS.ChainLeader(self.state, target_bits=a.get_int("minertargetbits", 0),
                                 state_path=os.path.join(self.datadir, "miner_state.json") if self.datadir else None)
         log.log_printf(f"miner service: {w.world_size} rank(s), backend {w.backend}, "
                        f"{'cpu' if cpu else 'gpu'} devices, {window} nonces per window")
         return MS.MiningService(dev, leader, window=window, watchdog_s=float(a.get("minerwatchdog", "120")),
-                                collective_timeout_s=timeout, max_failures=a.get_int("minermaxfailures", 3)).start()
+                                collective_timeout_s=timeout, max_failures=a.get_int("minermaxfailures", 3),
+                                rejoin=rejoiner).start()
 
     def _start_stratum(self, a: ArgsManager) -> None:
         """-stratumport: the Stratum server (miner/stratum_server.py) on -stratumbind, jobs paying
@@ -795,6 +814,10 @@ class Node:
                         p.wait(timeout=30)
                     except Exception:  # noqa: BLE001 — a follower that does not stop is killed
                         p.kill()
+                if getattr(self, "miner_rejoiner", None) is not None:
+                    self.miner_rejoiner.wait_followers(30)  # the stop packet ends them
+                    self.miner_rejoiner.close()  # the supervisor ends what is left of its followers, then itself
+                    self.miner_rejoiner = None
                 from .parallel import world as W
 
                 W.shutdown()

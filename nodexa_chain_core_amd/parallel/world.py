@@ -25,9 +25,19 @@ class World:
     device: torch.device = torch.device("cpu")
     group: object = None            # process group of the collectives (None = the default group)
     ranks: tuple[int, ...] = ()     # global ranks of the group members, index = rank in the group
+    ids: tuple[int, ...] = ()       # the members' ids (rank in the first world), index = rank in the group
 
     def global_rank(self, r: int) -> int:
         return self.ranks[r] if self.ranks else r
+
+    def global_id(self, r: int) -> int:
+        """The id rank `r` of the group had in the first world. It differs from global_rank once the
+        world has been re-formed (reform): the default group is then numbered 0..n-1 anew."""
+        return self.ids[r] if self.ids else self.global_rank(r)
+
+    @property
+    def member_ids(self) -> tuple[int, ...]:
+        return tuple(self.global_id(r) for r in range(self.world_size))
 
     @property
     def distributed(self) -> bool:
@@ -45,6 +55,9 @@ class World:
 
 _WORLD: World | None = None
 _INIT_GROUP = None  # the collective-timeout group init() made (None: the default group)
+_STORE = None       # the stand-alone rendezvous store of a world made with init(store_port=...)
+_EPOCH = 0          # membership epoch of the default group: its store prefix is "m<epoch>/"
+_INIT_KW: dict = {}  # what reform() needs to make the groups again
 
 
 def is_init_group(group) -> bool:
@@ -64,7 +77,8 @@ def rendezvous_timeout() -> int:
 
 def init(use_gpu: bool | None = None, timeout_s: int = 600, device_index: int | None = None,
          rank: int | None = None, world_size: int | None = None, elastic: bool = False,
-         force_collectives: bool | None = None, collective_timeout_s: float | None = None) -> World:
+         force_collectives: bool | None = None, collective_timeout_s: float | None = None,
+         store_port: int | None = None, membership: int = 0, ids=None) -> World:
     """Initialise from RANK/WORLD_SIZE/LOCAL_RANK (torchrun, or the node's spawned miner ranks)
     or single-process; `rank` / `world_size` override the environment. `device_index`: the GPU
     of this rank (default: LOCAL_RANK). `force_collectives` (env NODEXA_FORCE_COLLECTIVES=1):
@@ -76,8 +90,16 @@ def init(use_gpu: bool | None = None, timeout_s: int = 600, device_index: int | 
     sharded DAG gather of parallel/dag.py, batch verify) run on a group of their own created with
     that shorter timeout, so a rank lost mid-collective is detected in collective time, not
     rendezvous time. RCCL only: a gloo group connects its full mesh under its own timeout, and
-    host rehearsals whose ranks start seconds apart keep the default group."""
-    global _WORLD
+    host rehearsals whose ranks start seconds apart keep the default group.
+
+    `store_port` (opt-in; the node with -minerrejoin): rank 0 hosts a stand-alone TCPStore on that
+    port which lives as long as its process, every other rank connects to it, and the default group
+    is made over PrefixStore("m<membership>/", store) instead of env://. Such a world can be torn
+    down and made again with other members (reform), which a new process needs in order to join:
+    nothing can enter an existing default group. A rank that joins late passes the `membership` and
+    the member `ids` it was told, and its `rank` among them. Without `store_port` nothing changes
+    (torchrun worlds, bench.py)."""
+    global _WORLD, _EPOCH, _INIT_KW
     rank = int(os.environ.get("RANK", "0")) if rank is None else int(rank)
     world_size = int(os.environ.get("WORLD_SIZE", "1")) if world_size is None else int(world_size)
     if force_collectives is None:
@@ -114,18 +136,91 @@ def init(use_gpu: bool | None = None, timeout_s: int = 600, device_index: int | 
             # normal-priority stream can share a queue with the search stream, and a collective
             # queued there waits behind the ~117 ms search window already queued (profiles r4b)
             os.environ.setdefault("TORCH_NCCL_HIGH_PRIORITY", "1")
-        kw = {}
-        if use_gpu:
-            kw["device_id"] = device
-        dist.init_process_group(backend=backend, rank=rank, world_size=world_size,
-                                timeout=datetime.timedelta(seconds=timeout_s), **kw)
+        if store_port is not None:
+            connect_store(int(store_port), host=rank == 0 and not membership, timeout_s=timeout_s)
+        _EPOCH = int(membership)
+        _INIT_KW = {"backend": backend, "use_gpu": use_gpu, "device": device, "timeout_s": timeout_s,
+                    "collective_timeout_s": collective_timeout_s}
+        group = _make_groups(rank, world_size, timeout_s)
+    else:
+        group = _set_init_group(None)
+    ids = tuple(int(i) for i in ids) if ids is not None else tuple(range(world_size))
+    _WORLD = World(rank, world_size, local_rank, backend, device, group, tuple(range(world_size)), ids)
+    return _WORLD
+
+
+def _set_init_group(group):
     global _INIT_GROUP
-    group = None
-    if backend == "nccl" and collective_timeout_s is not None and collective_timeout_s < timeout_s:
-        group = dist.new_group(ranks=list(range(world_size)),
-                               timeout=datetime.timedelta(seconds=float(collective_timeout_s)))
     _INIT_GROUP = group
-    _WORLD = World(rank, world_size, local_rank, backend, device, group, tuple(range(world_size)))
+    return group
+
+
+def _make_groups(rank: int, world_size: int, timeout_s: float):
+    """The default group (over the store's current prefix when there is a store) and, on RCCL, the
+    collective-timeout group of init(). Returns the latter (None: the default group)."""
+    k = _INIT_KW
+    kw = {}
+    if k["use_gpu"]:
+        kw["device_id"] = k["device"]
+    if _STORE is not None:
+        kw["store"] = dist.PrefixStore(f"m{_EPOCH}/", _STORE)
+    dist.init_process_group(backend=k["backend"], rank=rank, world_size=world_size,
+                            timeout=datetime.timedelta(seconds=timeout_s), **kw)
+    group = None
+    ct = k["collective_timeout_s"]
+    if k["backend"] == "nccl" and ct is not None and ct < timeout_s:
+        group = dist.new_group(ranks=list(range(world_size)), timeout=datetime.timedelta(seconds=float(ct)))
+    return _set_init_group(group)
+
+
+def connect_store(port: int, host: bool = False, timeout_s: float | None = None):
+    """The stand-alone rendezvous store on 127.0.0.1:`port`: hosted (rank 0; it lives until this
+    process ends) or connected to. A rank that joins late connects before it has a world, to read
+    what it should prepare and to say that it is ready."""
+    global _STORE
+    if _STORE is None:
+        t = datetime.timedelta(seconds=rendezvous_timeout() if timeout_s is None else timeout_s)
+        _STORE = dist.TCPStore("127.0.0.1", int(port), None, bool(host), timeout=t, wait_for_workers=False)
+    return _STORE
+
+
+def store():
+    """The stand-alone store of this world (None: an env:// world, which cannot be re-formed)."""
+    return _STORE
+
+
+def epoch() -> int:
+    return _EPOCH
+
+
+def reform(members, membership: int, timeout_s: float | None = None) -> World:
+    """Make the world again over `members` (ids, rank 0's first) under store prefix
+    "m<membership>/": every group of this process, the loop communicator of miner/service.Comm
+    included, and the default group are destroyed, and the default group is initialised anew with
+    rank = members.index(this rank's id). Every member calls this on the same step (the survivors
+    on the packet that carries FLAG_REFORM, a newcomer through init(store_port=..., membership=...)),
+    so a world can grow back; shrink() stays the way to lose a rank. Needs a store world."""
+    global _WORLD, _EPOCH
+    w = get()
+    if _STORE is None or not w.collective:
+        raise RuntimeError("this world has no rendezvous store (init(store_port=...)): it cannot be re-formed")
+    members = [int(m) for m in members]
+    me = w.global_id(w.rank)
+    if me not in members:
+        raise RuntimeError(f"rank id {me} is not among the members {members}")
+    if int(membership) <= _EPOCH:
+        raise RuntimeError(f"membership {membership} is not after the current one ({_EPOCH})")
+    if _INIT_KW["use_gpu"]:
+        torch.cuda.synchronize(w.device)
+    if dist.is_initialized():
+        dist.destroy_process_group()
+    _set_init_group(None)
+    _EPOCH = int(membership)
+    t = _INIT_KW["timeout_s"] if timeout_s is None else timeout_s
+    rank = members.index(me)
+    group = _make_groups(rank, len(members), t)
+    _WORLD = World(rank, len(members), w.local_rank, w.backend, w.device, group,
+                   tuple(range(len(members))), tuple(members))
     return _WORLD
 
 
@@ -145,7 +240,9 @@ def shrink(survivors: list[int], timeout_s: int = 120) -> World:
         return w
     grp = dist.new_group(ranks=members, timeout=datetime.timedelta(seconds=timeout_s),
                          use_local_synchronization=True)
-    _WORLD = World(members.index(g), len(members), w.local_rank, w.backend, w.device, grp, tuple(members))
+    cur = list(w.ranks or range(w.world_size))
+    ids = tuple(w.global_id(cur.index(m)) for m in members)
+    _WORLD = World(members.index(g), len(members), w.local_rank, w.backend, w.device, grp, tuple(members), ids)
     return _WORLD
 
 
@@ -154,11 +251,13 @@ def get() -> World:
 
 
 def shutdown() -> None:
-    global _WORLD, _INIT_GROUP
+    global _WORLD, _INIT_GROUP, _STORE, _EPOCH
     if _WORLD is not None and _WORLD.collective and dist.is_initialized():
         dist.destroy_process_group()
     _WORLD = None
     _INIT_GROUP = None
+    _STORE = None
+    _EPOCH = 0
 
 
 def barrier() -> None:

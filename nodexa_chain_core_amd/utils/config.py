@@ -13,6 +13,11 @@ New engine flags: -gpus=0,1,.. -kawpowactivationtime= -equihash
 compiled kernel does not exist yet: wait for the compile, mine on the period-agnostic kernel until
 it is there (auto), or never compile (off). Any other value is an init error.
 
+-minerrejoin=<seconds> (default 0 = never): a GPU rank of the node's miner world that was evicted
+(-minermaxfailures) or hung (-minerwatchdog) is started again that long after its process ended and
+taken back into the world. -minerrejoinmax=<n> (default 3) such endings within
+-minerrejoinwindow=<seconds> (default 600) leave the GPU evicted. Not in torchrun worlds.
+
 -maxconnections=<n>: maintain at most <n> connections to peers in total (default 125), as in the
 reference: up to min(8, n) of them outbound, and n less the outbound slots and one more for
 inbound peers; at that limit a new inbound peer takes the place of an evictable one or is refused.
@@ -41,6 +46,21 @@ def kawpow_jit_mode(args: "ArgsManager") -> str:
         raise ValueError(f"Error: invalid -kawpowjit={mode} (expected {', '.join(KAWPOW_JIT_MODES[:-1])} "
                          f"or {KAWPOW_JIT_MODES[-1]})")
     return mode
+
+
+def miner_rejoin_args(args: "ArgsManager") -> tuple[float, int, float]:
+    """(-minerrejoin, -minerrejoinmax, -minerrejoinwindow), validated (ValueError with the init-error
+    text otherwise)."""
+    try:
+        delay = float(args.get("minerrejoin", "0") or 0)
+        n = int(args.get("minerrejoinmax", "3") or 3)
+        window = float(args.get("minerrejoinwindow", "600") or 600)
+    except ValueError:
+        raise ValueError("Error: -minerrejoin, -minerrejoinmax and -minerrejoinwindow take numbers") from None
+    if delay < 0 or n < 1 or window <= 0:
+        raise ValueError("Error: -minerrejoin must not be negative, -minerrejoinmax at least 1 and "
+                         "-minerrejoinwindow positive")
+    return delay, n, window
 
 
 class ArgsManager:
