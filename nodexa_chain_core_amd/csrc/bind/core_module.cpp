@@ -79,6 +79,19 @@ PYBIND11_MODULE(_core, m) {
     m.def("get_epoch_context", [](int e) { return std::const_pointer_cast<EpochContext>(get_epoch_context(e)); },
           py::call_guard<py::gil_scoped_release>());
     m.def("dataset_item_512", [](const EpochContext& c, u64 i) { return from_h512(dataset_item_512(c, i)); });
+    m.def("dag_digest", [](const py::buffer& data, u64 first_item, u64 chunk_items) {
+        const py::buffer_info b = data.request();
+        if (!PyBuffer_IsContiguous(b.view(), 'C')) throw std::invalid_argument("dag_digest: contiguous buffer");
+        const size_t len = size_t(b.size) * size_t(b.itemsize);
+        if (len % 64) throw std::invalid_argument("dag_digest: whole 64-byte items");
+        std::vector<u64> t;
+        {
+            py::gil_scoped_release nogil;
+            t = dag_digest(static_cast<const u8*>(b.ptr), first_item, len / 64, chunk_items);
+        }
+        return t;
+    }, py::arg("data"), py::arg("first_item"), py::arg("chunk_items") = 16384,
+       "DAG integrity digest: one u64 per global chunk the items [first_item, first_item + len/64) touch");
     m.def("dataset_item_2048", [](const EpochContext& c, u32 i) {
         Hash512 it[4];
         dataset_item_2048(c, i, it);

@@ -1,6 +1,9 @@
 #include "ethash.hpp"
 
+#include <algorithm>
 #include <cstdio>
+#include <cstring>
+#include <stdexcept>
 #include <list>
 #include <mutex>
 #include <string>
@@ -82,6 +85,39 @@ struct ItemState {
 };
 
 }  // namespace
+
+std::vector<u64> dag_digest(const u8* data, u64 first_item, u64 num_items, u64 chunk_items) {
+    if (chunk_items == 0) throw std::invalid_argument("dag_digest: chunk_items must be positive");
+    std::vector<u64> table;
+    if (num_items == 0) return table;
+    const u64 end = first_item + num_items;
+    for (u64 lo = first_item; lo < end;) {
+        const u64 hi = std::min(end, (lo / chunk_items + 1) * chunk_items);
+        u32 a_sum = 0, b_sum = 0;
+        for (u64 i = lo; i < hi; ++i) {
+            const u8* item = data + (i - first_item) * 64;
+            for (u32 j = 0; j < 16; ++j) {
+                u32 w;
+                std::memcpy(&w, item + 4 * j, 4);  // little-endian hosts only, as the rest of this file
+                const u32 g = u32(16 * i + j);
+                const u32 x = w ^ (g * 0x9E3779B1u);
+                u32 a = x * 0x85EBCA6Bu;
+                a ^= a >> 13;
+                a *= 0xC2B2AE35u;
+                a ^= a >> 16;
+                u32 b = (x ^ 0xA5A5A5A5u) * 0x27D4EB2Fu;
+                b ^= b >> 15;
+                b *= 0x165667B1u;
+                b ^= b >> 13;
+                a_sum += a;
+                b_sum += b;
+            }
+        }
+        table.push_back(u64(a_sum) | (u64(b_sum) << 32));
+        lo = hi;
+    }
+    return table;
+}
 
 Hash512 dataset_item_512(const EpochContext& ctx, u64 index) {
     ItemState s(ctx, index);

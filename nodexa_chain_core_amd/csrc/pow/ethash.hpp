@@ -17,6 +17,7 @@
 
 #include <atomic>
 #include <memory>
+#include <vector>
 #include <mutex>
 #include <string>
 
@@ -66,6 +67,14 @@ std::shared_ptr<const EpochContext> get_epoch_context(int epoch);
 Hash512 dataset_item_512(const EpochContext& ctx, u64 index);
 void dataset_item_1024(const EpochContext& ctx, u32 index, Hash512 out[2]);
 void dataset_item_2048(const EpochContext& ctx, u32 index, Hash512 out[4]);
+
+// DAG integrity digest (host model of hip/kernels/ethash_dag_check.hip). `data` holds `num_items`
+// 512-bit items as little-endian u32 words, the first of them DAG item `first_item`. Word j of item i
+// has global word index g = 16 i + j (low 32 bits); with x = w ^ g * 0x9E3779B1 two independent
+// bijective mixes a(x), b(x) are summed mod 2^32 over a chunk's words. One u64 A | B << 32 per chunk
+// of `chunk_items` items on the global grid that the range touches, each over the range's items
+// inside that chunk only: the sums commute, so partial digests of disjoint parts add up half by half.
+std::vector<u64> dag_digest(const u8* data, u64 first_item, u64 num_items, u64 chunk_items = 16384);
 
 // Host-side full dataset, filled lazily (thread-safe) or eagerly in parallel.
 class HostDag {

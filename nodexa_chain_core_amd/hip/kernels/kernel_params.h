@@ -28,6 +28,29 @@ struct EthashDagParams {
     uint32_t pad;
 };
 
+// DAG integrity digest (ethash_dag_check.hip): one workgroup per chunk of `chunk_items` items on the
+// global grid that [first_item, first_item + num_items) touches; workgroup c writes table[c].
+struct EthashDagDigestParams {
+    const void* dag;       // DAG base (item 0): positions are absolute, as in the build
+    uint64_t* table;       // out: A | B << 32 per chunk touched, first chunk = first_item / chunk_items
+    uint64_t first_item;
+    uint64_t num_items;
+    uint32_t chunk_items;
+    uint32_t pad;
+};
+
+// DAG audit: items first_item + k * stride, k < count, recomputed from the light cache and compared.
+struct EthashDagAuditParams {
+    const void* light;
+    void* dag;             // DAG base (item 0); written only when `repair` and only where bytes differ
+    uint32_t* out;         // [0] mismatching items, [1] lowest mismatching index (atomicMin), [2] repaired, [3] checked
+    uint64_t first_item;
+    uint64_t stride;
+    uint64_t count;
+    uint32_t light_items;
+    uint32_t repair;
+};
+
 struct KawpowShare {
     uint64_t nonce;
     uint32_t mix[8];    // mix digest words (storage order)

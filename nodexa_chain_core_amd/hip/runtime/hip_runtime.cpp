@@ -247,6 +247,54 @@ PYBIND11_MODULE(_hip, m) {
         k.launch_bytes(dim3(unsigned(grid)), dim3(block), 0, as_stream(stream), &args, sizeof(args));
     });
 
+    // table[c] = digest of the items of [first_item, first_item + num_items) inside global chunk
+    // first_item / chunk_items + c; `dag_items` bounds the range (the kernel reads exactly it)
+    m.def("launch_ethash_dag_digest", [](const Kernel& k, uintptr_t dag, uint64_t dag_items, uint64_t first_item,
+                                         uint64_t num_items, uint32_t chunk_items, uintptr_t table,
+                                         uint64_t table_entries, uintptr_t stream) {
+        if (chunk_items == 0) throw std::invalid_argument("dag digest: chunk_items must be positive");
+        if (first_item > dag_items || num_items > dag_items - first_item)
+            throw std::out_of_range("dag digest: range outside the DAG");
+        if (num_items == 0) return;
+        const uint64_t grid = (first_item + num_items - 1) / chunk_items - first_item / chunk_items + 1;
+        if (grid > table_entries) throw std::out_of_range("dag digest: table too small for the range's chunks");
+        if (grid > 0x7fffffffULL) throw std::invalid_argument("dag digest launch too large; split it");
+        EthashDagDigestParams p{};
+        p.dag = reinterpret_cast<const void*>(dag);
+        p.table = reinterpret_cast<uint64_t*>(table);
+        p.first_item = first_item;
+        p.num_items = num_items;
+        p.chunk_items = chunk_items;
+        k.launch_bytes(dim3(unsigned(grid)), dim3(256), 0, as_stream(stream), &p, sizeof(p));
+    });
+
+    // items first_item + k * stride, k < count; `out`: four u32 words the caller initialised to
+    // {0, 0xFFFFFFFF, 0, 0} (mismatches, lowest bad index, repaired, checked)
+    m.def("launch_ethash_dag_audit", [](const Kernel& k, uintptr_t light, uint32_t light_items, uintptr_t dag,
+                                        uint64_t dag_items, uint64_t first_item, uint64_t stride, uint64_t count,
+                                        bool repair, uintptr_t out, uintptr_t stream) {
+        if (count == 0) return;
+        if (stride == 0) throw std::invalid_argument("dag audit: stride must be positive");
+        if (first_item >= dag_items || (count - 1) > (dag_items - 1 - first_item) / stride)
+            throw std::out_of_range("dag audit: range outside the DAG");
+        struct {
+            EthashDagAuditParams p;
+            FastMod32 lmod;
+        } args{};
+        args.p.light = reinterpret_cast<const void*>(light);
+        args.p.dag = reinterpret_cast<void*>(dag);
+        args.p.out = reinterpret_cast<uint32_t*>(out);
+        args.p.first_item = first_item;
+        args.p.stride = stride;
+        args.p.count = count;
+        args.p.light_items = light_items;
+        args.p.repair = repair ? 1u : 0u;
+        args.lmod = make_fastmod(light_items);
+        const uint64_t grid = (count + 63) / 64;  // one item per lane quad, 64 per workgroup
+        if (grid > 0x7fffffffULL) throw std::invalid_argument("dag audit launch too large; split it");
+        k.launch_bytes(dim3(unsigned(grid)), dim3(256), 0, as_stream(stream), &args, sizeof(args));
+    });
+
     m.def("launch_kawpow_search", [](const Kernel& k, uintptr_t dag, uint32_t dag_items2048, uintptr_t results,
                                      const py::bytes& header, uint64_t start_nonce, uint64_t target,
                                      uint64_t num_nonces, uintptr_t stream, uintptr_t scratch,

@@ -249,13 +249,25 @@ class GpuSearchDevice:
 
     `jit_mode` (-kawpowjit, ops/kawpow.KawpowSearcher): "wait" stalls the loop in `submit` until a
     new period's kernel is compiled; "auto" runs such windows on the period-agnostic kernel and
-    swaps to the compiled one between two windows; "off" never compiles."""
+    swaps to the compiled one between two windows; "off" never compiles.
+
+    `dag_check` (-dagcheck, NODEXA_DAG_CHECK; default on): builds are checked (parallel/dag.DagCheck:
+    every received shard against its owner's digest, a sampled audit against the light cache) and
+    sealed with per-chunk digests. `dag_scrub_s` (-dagscrub, NODEXA_DAG_SCRUB_S; default 0 = off):
+    every so many seconds `submit` queues a digest of the current epoch's DAG on the side stream and
+    a later `submit` compares it with the seal; damaged chunks are repaired from the light cache
+    while the search goes on, and a chunk that cannot be repaired raises DeviceFault. Scrubbing
+    needs the seal, so it is off when `dag_check` is. With both off nothing of this runs and the
+    counters (`dag_scrubs`, `dag_bad_chunks`, `dag_repaired_items`, `dag_last_scrub_ms`,
+    `dag_check_events`) do not exist."""
 
     name = "gpu"
     MAX_EPOCHS = 2  # current + next (two 4 GiB DAGs are ~3 % of 288 GB)
 
     def __init__(self, device: int = 0, collective_dag: bool = False, jit_mode: str = "wait",
-                 joined_late: bool = False):
+                 joined_late: bool = False, dag_check: bool | None = None, dag_scrub_s: float | None = None):
+        import os
+
         import torch
 
         from ..ops import jit, runtime
@@ -293,6 +305,23 @@ class GpuSearchDevice:
         self.gen_ptr = self.h.host_words_alloc(1)
         self.generation = 0
         self.pending_build: dict[int, object] = {}
+        if dag_check is None:
+            dag_check = os.environ.get("NODEXA_DAG_CHECK", "1") != "0"
+        if dag_scrub_s is None:
+            dag_scrub_s = float(os.environ.get("NODEXA_DAG_SCRUB_S", "0") or 0)
+        self.dag_check = bool(dag_check)
+        self.dag_scrub_s = max(0.0, float(dag_scrub_s)) if self.dag_check else 0.0
+        if self.dag_check:
+            self.dag_checks: dict[int, object] = {}  # epoch -> DagCheck of a build not yet finished
+            self.dag_scrubs = 0           # scrubs compared with the seal
+            self.dag_bad_chunks = 0       # chunks found damaged, by a scrub or on arrival in a checked build
+            self.dag_repaired_items = 0   # items rewritten from the light cache
+            self.dag_last_scrub_ms = 0.0  # device time of the last scrub's digest
+            self.dag_check_events = 0     # scrubs and builds that found something
+            self.dag_bad_flag = False     # something was found since take_dag_bad() (the record's STATUS_DAG_BAD)
+            self._scrub_buf: dict = {}    # epoch -> (DeviceEpoch, device table, pinned table, two events)
+            self._scrub = None            # (epoch, DeviceEpoch, pinned table, start event, end event) in flight
+            self._scrub_last = time.monotonic()
 
     def close(self) -> None:
         if self.gen_ptr:
@@ -321,7 +350,9 @@ class GpuSearchDevice:
         with torch.cuda.device(self.device):
             e = DeviceEpoch(epoch, device=self.device, world_size=ws if collective else 1)
             with torch.cuda.stream(stream or self.stream):
-                if collective:
+                if self.dag_check:
+                    self.dag_checks[epoch] = pdag.build_dag_checked(e) if collective else pdag.build_solo_checked(e)
+                elif collective:
                     pdag.build_dag(e)
                 else:
                     e.build()
@@ -366,6 +397,10 @@ class GpuSearchDevice:
                 st.synchronize()
             if not e.l1_matches():
                 raise RuntimeError(f"gpu{self.device}: epoch {epoch} DAG failed its L1 self-check")
+            if self.dag_check:
+                self._finish_dag_check(epoch)
+                if self.dag_scrub_s:
+                    self._scrub_buffers(epoch, e)
         self.dag_build_s[epoch] = self.dag_build_s.get(epoch, 0.0) + time.perf_counter() - t0
         from ..ops import verify as V
 
@@ -375,6 +410,96 @@ class GpuSearchDevice:
             self.searchers.pop(old, None)
         self.epochs[epoch] = e
         return e
+
+    # ------------------------------------------------------------------ DAG integrity
+    def _finish_dag_check(self, epoch: int) -> None:
+        """After the build's streams are synchronised: compare the tables, repair, seal (raises
+        RuntimeError as the L1 check does when the DAG cannot be made right)."""
+        check = self.dag_checks.pop(epoch, None)
+        if check is None:
+            return
+        try:
+            check.finish()
+        except RuntimeError as exc:
+            raise RuntimeError(f"gpu{self.device}: epoch {epoch} DAG failed its build check: {exc}") from exc
+        if check.events:
+            self.dag_bad_chunks += check.bad_chunks
+            self.dag_repaired_items += check.repaired_items
+            self._dag_event(f"epoch {epoch} build check: {check.bad_chunks} received chunks damaged, "
+                            f"{check.repaired_items} items repaired")
+
+    def _dag_event(self, what: str) -> None:
+        from ..utils.log import log_printf
+
+        self.dag_check_events += 1
+        self.dag_bad_flag = True
+        log_printf(f"gpu{self.device}: DAG check: {what}")
+
+    def take_dag_bad(self) -> bool:
+        """A scrub or a build check found something since the last call (one record carries it)."""
+        if not self.dag_check:
+            return False
+        bad, self.dag_bad_flag = self.dag_bad_flag, False
+        return bad
+
+    def dag_counters(self) -> dict:
+        if not self.dag_check:
+            return {}
+        return {"dag_scrubs": self.dag_scrubs, "dag_bad_chunks": self.dag_bad_chunks,
+                "dag_repaired_items": self.dag_repaired_items, "dag_last_scrub_ms": round(self.dag_last_scrub_ms, 3),
+                "dag_check_events": self.dag_check_events}
+
+    def _scrub_buffers(self, epoch: int, e):
+        """The scrub's device and pinned tables and its two events, made once per epoch when the
+        epoch becomes resident: no allocation, pinned ones least of all, inside the mining loop."""
+        buf = self._scrub_buf.get(epoch)
+        if buf is None or buf[0] is not e:
+            torch = self.torch
+            with torch.cuda.device(self.device):
+                buf = (e, torch.empty(e.chunks, dtype=torch.int64, device=self.device),
+                       torch.empty(e.chunks, dtype=torch.int64).pin_memory(),
+                       torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            self._scrub_buf = {epoch: buf}
+        return buf
+
+    def _scrub_tick(self, epoch: int) -> None:
+        """Never blocks unless damage was found: queue a digest of the epoch's DAG on the side stream
+        when the interval has passed, or, once a queued one has finished, compare it with the seal."""
+        torch = self.torch
+        if self._scrub is None:
+            now = time.monotonic()
+            e = self.epochs.get(epoch)
+            if now - self._scrub_last < self.dag_scrub_s or e is None or e.seal_table is None:
+                return
+            self._scrub_last = now
+            buf = self._scrub_buffers(epoch, e)
+            _, table, host, ev0, ev1 = buf
+            side = int(self.side.cuda_stream)
+            with torch.cuda.device(self.device):
+                ev0.record(self.side)
+                e.digest(stream=side, out=table)
+                self.h.memcpy_async(host.data_ptr(), table.data_ptr(), table.numel() * 8, side, "dtoh")
+                ev1.record(self.side)
+            self._scrub = (epoch, e, host, ev0, ev1)
+            return
+        ep, e, host, ev0, ev1 = self._scrub
+        if not ev1.query():
+            return
+        self._scrub = None
+        self.dag_scrubs += 1
+        self.dag_last_scrub_ms = ev0.elapsed_time(ev1)
+        bad = e.chunks_differing(host)
+        if not bad:
+            return
+        # a repair writes correct bytes over wrong ones: the running search windows are safe
+        with torch.cuda.device(self.device), torch.cuda.stream(self.side):
+            left = e.repair_chunks(bad)
+        self.dag_bad_chunks += len(bad)
+        self.dag_repaired_items += e.last_repaired
+        self._dag_event(f"epoch {ep} scrub: chunks {bad} differ from the seal, {e.last_repaired} items repaired")
+        if left:
+            raise DeviceFault(f"gpu{self.device}: epoch {ep} DAG chunks {left} still differ from the seal after a "
+                              f"repair (damaged light cache?)")
 
     def searcher(self, height: int):
         from ..ops.kawpow import KawpowSearcher
@@ -402,6 +527,8 @@ class GpuSearchDevice:
     def submit(self, slot: int, work: Work, start: int, count: int) -> None:
         torch = self.torch
         s = self.searcher(work.height)
+        if self.dag_scrub_s:
+            self._scrub_tick(work.height // _core.EPOCH_LENGTH)
         b = s.block
         count = max(b, count // b * b)
         st = self.slot_streams[slot]

@@ -110,6 +110,7 @@ RECORD_SIZE = _REC_HEAD.size + RECORD_PAYLOAD                           # 5592
 STATUS_RESULT, STATUS_ALIVE, STATUS_VOTE = 1, 2, 4  # VOTE: next-epoch light cache ready
 STATUS_KERNEL_JIT, STATUS_KERNEL_GENERIC = 8, 16     # the KawPow kernel of the record's window (neither: not a GPU KawPow window)
 STATUS_EXHAUSTED = 32  # the rank has searched its whole nonce range of the current job (Work.rank_shift)
+STATUS_DAG_BAD = 64    # a DAG scrub or build check of this rank found damage in this step (search.GpuSearchDevice)
 _KERNEL_BITS = {"jit": STATUS_KERNEL_JIT, "generic": STATUS_KERNEL_GENERIC}
 
 
@@ -139,6 +140,7 @@ class RankRecord:
     kernel: str = ""  # "jit" / "generic": the KawPow kernel of this window on a GPU rank
     dropped: int = 0  # shares of this window lost to the device ring or to the record's share cap
     exhausted: bool = False  # the rank's nonce range of the current job is used up
+    dag_bad: bool = False    # the rank's DAG check found (and repaired) damage in this step
 
 
 def _as_record(r) -> RankRecord:
@@ -149,12 +151,13 @@ def _as_record(r) -> RankRecord:
 
 
 def pack_record(res: SlotResult | None, *, coll_ms: float = 0.0, failures: int = 0, epochs=(),
-                alive: bool = True, device: int = -1, vote: bool = False, exhausted: bool = False) -> bytes:
+                alive: bool = True, device: int = -1, vote: bool = False, exhausted: bool = False,
+                dag_bad: bool = False) -> bytes:
     out = bytearray(RECORD_SIZE)
     ep = sorted(epochs)
     lo, n = (ep[0], ep[-1] - ep[0] + 1) if ep else (0, 0)
     status = (STATUS_RESULT if res is not None else 0) | (STATUS_ALIVE if alive else 0) | (STATUS_VOTE if vote else 0)
-    status |= STATUS_EXHAUSTED if exhausted else 0
+    status |= (STATUS_EXHAUSTED if exhausted else 0) | (STATUS_DAG_BAD if dag_bad else 0)
     if res is None:
         _REC_HEAD.pack_into(out, 0, 0, 0, 0, 0, 0, 0, int(coll_ms * 1e3), failures, lo, n, status, device)
         return bytes(out)
@@ -220,7 +223,7 @@ def unpack_record(raw: bytes) -> RankRecord:
     return RankRecord(job, hashes, shares, algo, dev_us / 1e3, aborted, coll_us / 1e3, failures,
                       list(range(lo, lo + nep)), bool(status & STATUS_RESULT), bool(status & STATUS_ALIVE), device,
                       "jit" if status & STATUS_KERNEL_JIT else "generic" if status & STATUS_KERNEL_GENERIC else "",
-                      n - len(shares), bool(status & STATUS_EXHAUSTED))
+                      n - len(shares), bool(status & STATUS_EXHAUSTED), bool(status & STATUS_DAG_BAD))
 
 
 class Comm:
@@ -847,11 +850,12 @@ class MiningService:
             self._device_failure(e)
             res = None
         vote = self._next_epoch_vote()
+        dag = self._kawpow_dag()
         # resident or being built: what a peer needs to know to choose how it builds (search.dag_build_mode)
         rec = pack_record(res, coll_ms=self.coll_ms, failures=self.failures,
                           epochs=set(self.dev.resident_epochs()) | set(self.dev.pending_epochs()),
                           alive=self.dev_alive, device=int(getattr(self.dev, "device", -1)), vote=bool(vote),
-                          exhausted=exhausted)
+                          exhausted=exhausted, dag_bad=dag.take_dag_bad() if dag is not None else False)
         tc = time.perf_counter()
         gathered = self.comm.all_gather(rec)
         coll = time.perf_counter() - tc
@@ -878,7 +882,8 @@ class MiningService:
                 self.rank_hashes[i] = self.rank_hashes.get(i, 0) + rec_i.hashes
                 self.rank_rates.setdefault(i, RateMeter()).add(rec_i.hashes, now)
                 info = self.rank_info_raw.setdefault(i, {"aborted": 0, "windows": 0, "jit_windows": 0,
-                                                         "generic_windows": 0})
+                                                         "generic_windows": 0, "dag_check_events": 0})
+                info["dag_check_events"] += rec_i.dag_bad
                 info.update(alive=rec_i.alive, failures=rec_i.failures, epochs=rec_i.epochs, device=rec_i.device,
                             coll_ms=rec_i.coll_ms)
                 if rec_i.has_result:
@@ -911,6 +916,11 @@ class MiningService:
             self._reform(new.nonce_base)
         self.last_step_ms = (time.perf_counter() - t0) * 1e3
         return not new.stop
+
+    def _kawpow_dag(self):
+        """This rank's KawPow device if it checks its DAGs (search.GpuSearchDevice with dag_check)."""
+        kp = getattr(self.dev, "kawpow", None)
+        return kp if getattr(kp, "dag_check", False) else None
 
     # ---------------------------------------------------------------- growing the world back
     def _reform_due(self) -> int | None:
@@ -975,6 +985,8 @@ class MiningService:
         stats = getattr(self.leader, "per_rank", {}) if self.leader is not None else {}
         ids = list(self.member_ids)
         away = [g for g in (self.rejoin.known_ids() if self.rejoin is not None else []) if g not in ids]
+        dag = self._kawpow_dag()
+        local = dag.dag_counters() if dag is not None else {}  # the local device's own counters
         for r, gid in [(r, g) for r, g in enumerate(ids)] + [(-1, g) for g in away]:
             info = self.rank_info_raw.get(gid, {})
             rs = stats.get(gid, {})
@@ -1011,7 +1023,10 @@ class MiningService:
                 "generic_windows": info.get("generic_windows", 0),
                 "jit_windows": info.get("jit_windows", 0),
                 "failures": info.get("failures", 0),
+                "dag_check_events": info.get("dag_check_events", 0),
             })
+            if r == self.rank:
+                out[-1].update({k: v for k, v in local.items() if k != "dag_check_events"})
         return out
 
     # ---------------------------------------------------------------- failures
@@ -1302,6 +1317,7 @@ class Miner:
         self._last_hashes = 0
         self._last_shares = 0
         self._last_kernel_windows = {"jit": 0, "generic": 0}
+        self._last_dag = {"dag_scrubs": 0, "dag_bad_chunks": 0, "dag_repaired_items": 0}
 
     @classmethod
     def local(cls, state, *, window: int = 4096, fail_rate: float = 0.0, drop_rate: float = 0.0,
@@ -1339,6 +1355,13 @@ class Miner:
             if n > self._last_kernel_windows[kind]:
                 self.metrics.inc(f"miner_kawpow_{kind}_windows_total", n - self._last_kernel_windows[kind], worker="service")
                 self._last_kernel_windows[kind] = n
+        dag = self.service._kawpow_dag()
+        if dag is not None:
+            now = dag.dag_counters()
+            for key, last in self._last_dag.items():
+                if now[key] > last:
+                    self.metrics.inc(key + "_total", now[key] - last, worker="service")
+                    self._last_dag[key] = now[key]
 
     def generate(self, script_pubkey: bytes, nblocks: int, max_tries: int = 1_000_000) -> list[str]:
         """generateBlocks: the new block hashes (display hex), mined by the service."""

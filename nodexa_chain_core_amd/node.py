@@ -35,7 +35,7 @@ from .rpc import (methods, methods_assets, methods_ext, methods_index, methods_m
                   methods_wallet_ext)
 from .rpc.server import RPCServer, RPCTable, delete_cookie, make_cookie
 from .utils import log, metrics
-from .utils.config import ArgsManager, gpu_list, kawpow_jit_mode, miner_rejoin_args
+from .utils.config import ArgsManager, dag_check_args, gpu_list, kawpow_jit_mode, miner_rejoin_args
 
 _core = core()
 
@@ -401,6 +401,14 @@ class Node:
             jit_mode = kawpow_jit_mode(a)
         except ValueError as e:
             raise SystemExit(str(e))
+        try:  # before any rank is spawned: the followers inherit the environment
+            dag_check, dag_scrub_s = dag_check_args(a)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        if dag_check is not None:
+            os.environ["NODEXA_DAG_CHECK"] = "1" if dag_check else "0"
+        if dag_scrub_s is not None:
+            os.environ["NODEXA_DAG_SCRUB_S"] = repr(dag_scrub_s)
         timeout = float(a.get("minercollectivetimeout", "60"))
         fail, drop = float(a.get("gpufailrate", "0") or 0), float(a.get("dropshare", "0") or 0)
         self.miner_procs = []
@@ -939,6 +947,14 @@ class Node:
         from .models import verify
 
         return list(verify.verify_headers(self.params, headers, gpus=self.gpus))
+
+    def verify_dag(self, epoch: int | None = None, full: bool = False, repair: bool = False) -> list[dict]:
+        """verifydag: check the DAGs resident on the node's GPU (ops/verify.verify_dag); [] without one."""
+        if not self.gpus:
+            return []
+        from .ops import verify as V
+
+        return V.verify_dag(self.gpus[0], epoch, full=full, repair=repair)
 
     def equihash_solve(self, inp: bytes) -> list[list[int]]:
         if self.gpus:

@@ -12,6 +12,8 @@ RCCL ("DAG sharding").
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
+
 import torch
 
 from .. import _core
@@ -21,6 +23,37 @@ from ..utils.trace import traced
 # 512-bit items per launch: keeps a single dispatch well under a second even
 # at epoch 384 while still giving >> 256 CUs x 8 waves of work.
 _DAG_CHUNK = 1 << 22
+# DAG integrity (hip/kernels/ethash_dag_check.hip): items per digest chunk (1 MiB, global grid)
+DAG_CHUNK_ITEMS = 16384
+_U64 = (1 << 64) - 1
+
+
+@dataclass(frozen=True)
+class AuditResult:
+    """The four words an audit leaves on the device."""
+    mismatches: int
+    first_bad: int | None  # lowest mismatching item index
+    repaired: int
+    checked: int
+
+    @classmethod
+    def parse(cls, words) -> "AuditResult":
+        w = [int(x) & 0xFFFFFFFF for x in (words.tolist() if hasattr(words, "tolist") else words)]
+        return cls(w[0], None if w[0] == 0 else w[1], w[2], w[3])
+
+    @property
+    def clean(self) -> bool:
+        return self.mismatches == 0
+
+
+def chunk_span(first: int, count: int, chunk_items: int = DAG_CHUNK_ITEMS) -> tuple[int, int]:
+    """(first chunk, number of chunks) of the global grid that items [first, first + count) touch."""
+    if count <= 0:
+        return first // chunk_items, 0
+    c0 = first // chunk_items
+    return c0, (first + count - 1) // chunk_items - c0 + 1
+
+
 # hashes per 16-lane row of ethash_hash_batch (EH_HASHES in hip/kernels/ethash_hashimoto.hip)
 EH_HASHES = 2
 
@@ -52,6 +85,10 @@ class DeviceEpoch:
                                             device=self.device)
                 self.dag = self._storage[:self.dag_bytes]
         self.built = False
+        self._audit_init = None  # pinned {0, 0xFFFFFFFF, 0, 0}: an audit's four words before it runs
+        self.last_repaired = 0
+        self._seal_pending = None
+        self.seal_table: torch.Tensor | None = None  # per-chunk digests of the whole DAG, on the host (seal())
 
     # ------------------------------------------------------------------
     def shard_items(self, world: int) -> int:
@@ -91,6 +128,16 @@ class DeviceEpoch:
         if shard is None:
             self.built = True
 
+    def build_checked(self, stream: int | None = None):
+        """`build()` followed by a sampled audit and `seal()`, all queued without a host wait on the
+        current stream. Returns the parallel.dag.DagCheck to `finish()` after a synchronisation."""
+        from ..parallel import dag as pdag
+
+        if stream is not None:
+            with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=self.device)):
+                return pdag.build_solo_checked(self)
+        return pdag.build_solo_checked(self)
+
     def mark_built(self) -> None:
         self.built = True
 
@@ -99,6 +146,139 @@ class DeviceEpoch:
         dev = self.dag[:16384].cpu().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
         ref = torch.tensor(self.ctx.l1, dtype=torch.int64)
         return bool(torch.equal(dev, ref))
+
+    # ------------------------------------------------------------------ integrity
+    @property
+    def chunks(self) -> int:
+        return (self.items512 + DAG_CHUNK_ITEMS - 1) // DAG_CHUNK_ITEMS
+
+    def _range(self, first: int, count: int | None) -> tuple[int, int]:
+        if self.dag is None:
+            raise ValueError("light-only DeviceEpoch has no DAG to check")
+        first = int(first)
+        count = self.items512 - first if count is None else int(count)
+        if first < 0 or count < 0 or first + count > self.items512:
+            raise ValueError(f"items [{first}, {first + count}) are outside the DAG of {self.items512}")
+        return first, count
+
+    def digest(self, first: int = 0, count: int | None = None, stream: int | None = None,
+               out: torch.Tensor | None = None) -> torch.Tensor:
+        """Per-chunk digests (`_core.dag_digest`'s definition) of items [first, first + count), as a
+        device int64 tensor with one entry per chunk of the global grid that the range touches.
+        Queued on the stream, no host wait. `out`: write into this int64 tensor's leading entries
+        (it is returned whole) instead of a new one."""
+        first, count = self._range(first, count)
+        n = chunk_span(first, count)[1]
+        with torch.cuda.device(self.device):
+            k = runtime.static_kernel("ethash_dag_check", "ethash_dag_digest")
+            table = torch.empty(n, dtype=torch.int64, device=self.device) if out is None else out
+            if table.dtype != torch.int64 or table.numel() < n:
+                raise ValueError("digest table must be int64 with one entry per chunk touched")
+            s = runtime.current_stream_handle() if stream is None else stream
+            runtime.hip().launch_ethash_dag_digest(k, self.dag.data_ptr(), self.items512, first, count,
+                                                   DAG_CHUNK_ITEMS, table.data_ptr(), table.numel(), s)
+        return table
+
+    def audit(self, first: int = 0, count: int | None = None, stride: int = 1, repair: bool = False,
+              stream: int | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+        """Recompute items first + k * stride (k < count; default: as many as fit) from the light
+        cache and compare them with the resident ones; with `repair`, rewrite the 16-byte pieces
+        that differ. Returns the device int32 tensor of four words (AuditResult.parse), queued on
+        the stream with no host wait. `out`: accumulate into this tensor (already initialised)."""
+        stride = int(stride)
+        if stride < 1:
+            raise ValueError("audit stride must be positive")
+        first, _ = self._range(first, 0)
+        fit = (self.items512 - first + stride - 1) // stride
+        count = fit if count is None else int(count)
+        if count < 0 or count > fit:
+            raise ValueError("audit range is outside the DAG")
+        with torch.cuda.device(self.device):
+            k = runtime.static_kernel("ethash_dag_check", "ethash_dag_audit")
+            s = runtime.current_stream_handle() if stream is None else stream
+            h = runtime.hip()
+            if out is None:
+                if self._audit_init is None:
+                    self._audit_init = torch.tensor([0, -1, 0, 0], dtype=torch.int32).pin_memory()
+                out = torch.empty(4, dtype=torch.int32, device=self.device)
+                h.memcpy_async(out.data_ptr(), self._audit_init.data_ptr(), 16, s, "htod")
+            pos = 0
+            while pos < count:
+                n = min(_DAG_CHUNK, count - pos)
+                h.launch_ethash_dag_audit(k, self.light.data_ptr(), int(self.ctx.light_items), self.dag.data_ptr(),
+                                          self.items512, first + pos * stride, stride, n, bool(repair),
+                                          out.data_ptr(), s)
+                pos += n
+        return out
+
+    def _host(self, t: torch.Tensor, stream: int | None) -> torch.Tensor:
+        if stream is not None:  # a raw stream handle: torch's copy below runs on its own current stream
+            runtime.hip().stream_synchronize(stream)
+        return t.cpu()
+
+    def audit_result(self, first: int = 0, count: int | None = None, stride: int = 1, repair: bool = False,
+                     stream: int | None = None) -> AuditResult:
+        """`audit`, waited for and parsed."""
+        return AuditResult.parse(self._host(self.audit(first, count, stride, repair, stream), stream))
+
+    def copy_to_pinned(self, t: torch.Tensor, stream: int | None = None) -> torch.Tensor:
+        """Queue a copy of device tensor `t` to new pinned host memory; valid once the stream got there."""
+        host = torch.empty(t.shape, dtype=t.dtype).pin_memory()
+        with torch.cuda.device(self.device):
+            s = runtime.current_stream_handle() if stream is None else stream
+            runtime.hip().memcpy_async(host.data_ptr(), t.data_ptr(), t.numel() * t.element_size(), s, "dtoh")
+        host._nx_src = t  # the device tensor lives until the copy has been consumed
+        return host
+
+    def seal(self, stream: int | None = None, wait: bool = True) -> torch.Tensor | None:
+        """Digest the whole DAG and keep the table (host int64) as `seal_table`: what `check_seal`
+        compares later digests with. `wait=False` only queues the digest and its copy to pinned
+        memory; `finish_seal()` adopts it once the stream has been synchronised."""
+        self._seal_pending = self.copy_to_pinned(self.digest(stream=stream), stream)
+        if not wait:
+            return None
+        with torch.cuda.device(self.device):
+            runtime.hip().stream_synchronize(runtime.current_stream_handle() if stream is None else stream)
+        return self.finish_seal()
+
+    def finish_seal(self) -> torch.Tensor:
+        self.seal_table = self._seal_pending.clone()
+        self._seal_pending = None
+        return self.seal_table
+
+    def check_seal(self, stream: int | None = None) -> list[int]:
+        """The chunks whose digest differs from the seal now."""
+        if self.seal_table is None:
+            raise RuntimeError("the DAG has no seal")
+        return self.chunks_differing(self._host(self.digest(stream=stream), stream))
+
+    def chunks_differing(self, table: torch.Tensor) -> list[int]:
+        """Chunks at which a whole-DAG digest table (host) differs from the seal."""
+        return torch.nonzero(table != self.seal_table).flatten().tolist()
+
+    def repair_chunks(self, chunks, stream: int | None = None) -> list[int]:
+        """Audit the listed chunks with repair, digest them again and return those that still differ
+        from the seal (a damaged light cache, or a seal taken of a damaged DAG). The repaired item
+        count of the call is left in `last_repaired`."""
+        if self.seal_table is None:
+            raise RuntimeError("the DAG has no seal")
+        chunks = sorted({int(c) for c in chunks})
+        words = None
+        with torch.cuda.device(self.device):
+            table = torch.empty(len(chunks), dtype=torch.int64, device=self.device)
+        for i, c in enumerate(chunks):
+            if not 0 <= c < self.chunks:
+                raise ValueError(f"chunk {c} is outside the DAG")
+            first = c * DAG_CHUNK_ITEMS
+            n = min(DAG_CHUNK_ITEMS, self.items512 - first)
+            words = self.audit(first, n, repair=True, stream=stream, out=words)
+            self.digest(first, n, stream=stream, out=table[i:i + 1])
+        if not chunks:
+            self.last_repaired = 0
+            return []
+        now = self._host(table, stream)
+        self.last_repaired = AuditResult.parse(words.cpu()).repaired
+        return [c for c, d in zip(chunks, now.tolist()) if d != int(self.seal_table[c])]
 
     def item512(self, index: int) -> bytes:
         return bytes(self.dag[index * 64:(index + 1) * 64].cpu().numpy().tobytes())

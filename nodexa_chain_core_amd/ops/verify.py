@@ -66,9 +66,13 @@ def is_resident(device: int, epoch: int) -> bool:
 def share_epoch(device: int, epoch: int, e: DeviceEpoch) -> None:
     """Offer a DAG built elsewhere on `device` (the miner's, miner/search.GpuSearchDevice) to batch
     verify: a mining node then verifies the current epoch's headers against the DAG it mines on
-    instead of building a second 4 GiB copy (read-only on both sides)."""
+    instead of building a second 4 GiB copy (read-only on both sides). A sealed DAG (a checked
+    build, ops/ethash.DeviceEpoch.seal) takes the place of an unsealed one: verification then reads
+    the copy that the miner's scrub watches."""
     with _epochs_lock:
-        _epochs.setdefault((device, epoch), e)
+        have = _epochs.get((device, epoch))
+        if have is None or (have.seal_table is None and e.seal_table is not None):
+            _epochs[(device, epoch)] = e
 
 
 def prefetch_contexts(epochs, device: int) -> None:
@@ -103,6 +107,45 @@ def register_resident(epoch_dev: DeviceEpoch) -> None:
     if epoch_dev.built and epoch_dev.dag is not None:
         with _epochs_lock:
             _epochs[(epoch_dev.device.index, epoch_dev.epoch)] = epoch_dev
+
+
+VERIFYDAG_STRIDE = 64  # verifydag without `full`: one item in 64 is recomputed
+
+
+def resident_dags(device: int) -> list[DeviceEpoch]:
+    """The built DAGs of `device` in the registry (the miner's shared ones included), by epoch."""
+    with _epochs_lock:
+        found = [e for (d, _), e in _epochs.items() if d == device and e.dag is not None]
+    return sorted(found, key=lambda e: e.epoch)
+
+
+def verify_dag(device: int, epoch: int | None = None, full: bool = False, repair: bool = False) -> list[dict]:
+    """The `verifydag` RPC: for every resident DAG of `device` (or only `epoch`'s), the chunks that
+    differ from the seal (when the build was sealed) and an audit against the light cache of one item
+    in VERIFYDAG_STRIDE, or of every item with `full`; with `repair` what differs is rewritten. Runs
+    on a stream of its own beside mining: it only reads, and a repair writes correct bytes."""
+    import time
+
+    from .ethash import AuditResult
+
+    out = []
+    for e in resident_dags(device):
+        if epoch is not None and e.epoch != int(epoch):
+            continue
+        t0 = time.perf_counter()
+        with torch.cuda.device(device):
+            st = _side_stream(device, 3)
+            s = int(st.cuda_stream)
+            sealed = e.seal_table is not None
+            bad = e.check_seal(stream=s) if sealed else []
+            res = e.audit_result(0, None, 1 if full else VERIFYDAG_STRIDE, repair=repair, stream=s)
+            if sealed and repair and bad:
+                e.repair_chunks(bad, stream=s)
+                res = AuditResult(res.mismatches, res.first_bad, res.repaired + e.last_repaired, res.checked)
+        out.append({"epoch": e.epoch, "items": e.items512, "chunks": e.chunks, "sealed": sealed, "bad_chunks": bad,
+                    "audited": res.checked, "mismatches": res.mismatches, "first_bad": res.first_bad,
+                    "repaired": res.repaired, "ms": round((time.perf_counter() - t0) * 1e3, 3)})
+    return out
 
 
 def _pack_jobs(block_numbers, header_hashes, nonces) -> np.ndarray:

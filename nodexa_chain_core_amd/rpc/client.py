@@ -19,7 +19,7 @@ import urllib.parse
 from ..utils.config import ArgsManager
 
 # params parsed as JSON when given as CLI strings, by method and position: the reference's
-# vRPCConvertParams (src/rpc/client.cpp), plus this engine's verifyheaders
+# vRPCConvertParams (src/rpc/client.cpp), plus this engine's verifyheaders and verifydag
 _CONVERT_POSITIONS = {
     "issue": (1, 4, 5, 6), "issuerestrictedasset": (1, 5, 6, 7), "issuequalifierasset": (1, 4),
     "reissuerestrictedasset": (1, 3, 6, 7), "issueunique": (1, 2), "transfer": (1, 4), "transferfromaddress":
@@ -46,6 +46,7 @@ _CONVERT_POSITIONS = {
     "requestsnapshot": (1,), "getsnapshotrequest": (1,), "listsnapshotrequests": (1,), "cancelsnapshotrequest":
     (1,), "distributereward": (1, 3), "getdistributestatus": (1, 3), "getsnapshot": (1,), "purgesnapshot": (1,),
     "stop": (0,), "getkawpowhash": (3,), "verifyheaders": (0,),
+    "verifydag": (0, 1, 2),
 }
 CONVERT = {(m, i) for m, ix in _CONVERT_POSITIONS.items() for i in ix}
 

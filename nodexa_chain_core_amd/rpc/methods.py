@@ -6,7 +6,7 @@ src/rpc/misc.cpp:1469). Result keys follow the reference, including the
 KawPow additions (getblock: headerhash / mixhash / nonce64; getblocktemplate:
 pprpcheader / pprpcepoch, CommunityAutonomousAddress / Value; getkawpowhash:
 result / digest / mix_hash / info / meets_target; pprpcsb: BIP22 results).
-Engine additions are in the "gpu" category (getgpuinfo, equihash*, verifyheaders).
+Engine additions are in the "gpu" category (getgpuinfo, equihash*, verifyheaders, verifydag).
 """
 from __future__ import annotations
 
@@ -696,6 +696,17 @@ def register(table, node) -> None:  # noqa: C901 — one table, like the referen
         hdrs = [_core.BlockHeader.deserialize(bytes.fromhex(x), params.kawpow_activation_time) for x in p[0]]
         return node.verify_headers(hdrs)
 
+    def rpc_verifydag(p):
+        """verifydag ( epoch full repair ) — check the KawPow DAGs resident on the node's GPU.
+        For each (or only `epoch`): the 1 MiB chunks whose digest differs from the seal taken after the
+        build, and an audit that recomputes one item in 64 from the light cache (every item with
+        full=true); repair=true rewrites what differs. Returns [{epoch, items, chunks, sealed,
+        bad_chunks, audited, mismatches, first_bad, repaired, ms}], [] without a GPU or a resident DAG.
+        A DAG built with -dagcheck=0 has no seal and is only audited."""
+        epoch = None if len(p) < 1 or p[0] is None else int(p[0])
+        return node.verify_dag(epoch, full=bool(p[1]) if len(p) > 1 else False,
+                               repair=bool(p[2]) if len(p) > 2 else False)
+
     def rpc_equihashsolve(p):
         """equihashsolve "input_hex" — solve Equihash(200,9) for a 112-byte input (GPU if available)."""
         _need(p, 1, 'equihashsolve "input_hex"')
@@ -711,6 +722,7 @@ def register(table, node) -> None:  # noqa: C901 — one table, like the referen
         return {"valid": ok, "reason": why}
 
     for name, fn, args in [("getgpuinfo", rpc_getgpuinfo, ()), ("verifyheaders", rpc_verifyheaders, ("headers",)),
+                           ("verifydag", rpc_verifydag, ("epoch", "full", "repair")),
                            ("equihashsolve", rpc_equihashsolve, ("input",)),
                            ("equihashverify", rpc_equihashverify, ("input", "solution"))]:
         table.append("gpu", name, fn, args)

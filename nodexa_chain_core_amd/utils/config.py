@@ -18,6 +18,12 @@ it is there (auto), or never compile (off). Any other value is an init error.
 taken back into the world. -minerrejoinmax=<n> (default 3) such endings within
 -minerrejoinwindow=<seconds> (default 600) leave the GPU evicted. Not in torchrun worlds.
 
+-dagcheck=0|1 (default 1; NODEXA_DAG_CHECK): the KawPow GPU miner checks every DAG it builds (each
+received shard against its owner's digest, a sampled audit against the light cache) and seals it
+with per-chunk digests. -dagscrub=<seconds> (default 0 = off; NODEXA_DAG_SCRUB_S): while mining,
+digest the resident DAG that often, compare with the seal and repair damaged chunks from the light
+cache; needs -dagcheck=1. The flags reach every rank of the miner world through those variables.
+
 -maxconnections=<n>: maintain at most <n> connections to peers in total (default 125), as in the
 reference: up to min(8, n) of them outbound, and n less the outbound slots and one more for
 inbound peers; at that limit a new inbound peer takes the place of an evictable one or is refused.
@@ -61,6 +67,22 @@ def miner_rejoin_args(args: "ArgsManager") -> tuple[float, int, float]:
         raise ValueError("Error: -minerrejoin must not be negative, -minerrejoinmax at least 1 and "
                          "-minerrejoinwindow positive")
     return delay, n, window
+
+
+def dag_check_args(args: "ArgsManager") -> tuple[bool | None, float | None]:
+    """(-dagcheck, -dagscrub), validated (ValueError with the init-error text otherwise); None for a
+    flag that was not given (the environment's NODEXA_DAG_CHECK / NODEXA_DAG_SCRUB_S then decide)."""
+    check = args.get("dagcheck")
+    if check is not None and check not in ("0", "1", ""):
+        raise ValueError(f"Error: invalid -dagcheck={check} (expected 0 or 1)")
+    scrub = args.get("dagscrub")
+    try:
+        scrub_s = None if scrub is None else float(scrub or 0)
+    except ValueError:
+        raise ValueError("Error: -dagscrub takes a number of seconds") from None
+    if scrub_s is not None and scrub_s < 0:
+        raise ValueError("Error: -dagscrub must not be negative")
+    return (None if check is None else check != "0"), scrub_s
 
 
 class ArgsManager:
