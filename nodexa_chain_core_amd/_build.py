@@ -233,7 +233,8 @@ def build_hip_runtime(force: bool = False, jobs: int = 8) -> str:
     return out
 
 
-def hipcc_genco(src: str, out: str, defines: list[str] | None = None, includes: list[str] | None = None) -> None:
+def hipcc_genco(src: str, out: str, defines: list[str] | None = None, includes: list[str] | None = None,
+                extra: list[str] | None = None) -> None:
     cmd = [os.path.join(ROCM, "bin", "hipcc"), "--genco", "--offload-arch=" + ARCH, "-O3", "-std=c++17",
            "-mcode-object-version=5", "-ffp-contract=fast", "-I" + os.path.join(HIPDIR, "kernels")]
     for d in defines or []:
@@ -245,7 +246,7 @@ def hipcc_genco(src: str, out: str, defines: list[str] | None = None, includes: 
         cmd.append("-D" + d)
     for i in includes or []:
         cmd.append("-I" + i)
-    _run(cmd + [src, "-o", out])
+    _run(cmd + (extra or []) + [src, "-o", out])
 
 
 def build_kernels(force: bool = False, jobs: int = 8) -> list[str]:

@@ -28,8 +28,11 @@
 //     program bakes every index in), so they are scalarised into VGPRs.
 //   * everything not needed inside the round loop leaves the VGPR file: each
 //     hash's 8 digest words are parked in the 8 VGPRs of the lane that owns it,
-//     and the keccak state words 2..7 are recomputed for the final absorb
-//     instead of being held live.
+//     and the seed keccak's state words 0..4 wait in LDS (15 KiB beside the L1)
+//     for the final absorb; words 0 and 1, every hash's mix seed, are read from
+//     there by the group instead of being held live and shuffled. 1821 VALU per
+//     nonce; what the rate follows is less the count than what a wave waits
+//     for between two hashes (profiles/README r11).
 //   * each round's 256-byte DAG item is one coalesced 16 B/lane load by the
 //     group (lane l takes words ((l^r)%16)*4..+3).
 #include "kernel_params.h"
@@ -279,6 +282,9 @@ NX_DEV void kp_final(const uint32_t st2[8], const uint32_t digest[8], uint32_t o
 // The group's 16 hashes, KP_HASHES at a time. `st0/st1` are this thread's own
 // nonce seed words (hash h's seed lives in lane h). Each finished hash's 8
 // digest words go to `own` of the lane that owns the hash (8 DPP broadcasts).
+// With SEEDS_IN_LDS the two seed words are not held in VGPRs: `seeds` is the group's row of
+// parked words in LDS (st0 of lane h at seeds[h], st1 one KP_BLOCK plane on), and each hash's
+// seed is one LDS read instead of two ds_bpermute of values that live across the round loop.
 // One ProgPoW round with the round index known mod 16 (J): the item index comes
 // from lane J of the row via DPP and the lane's 16-byte slice is lane ^ J.
 template <int J>
@@ -303,15 +309,17 @@ NX_DEV void kp_round_c(uint32_t (&mx)[KP_HASHES][32], const KP_DAG& dag,
     for (int k = 0; k < KP_HASHES; ++k) KAWPOW_DAG_MERGE(d[k], mx[k]);
 }
 
+template <bool SEEDS_IN_LDS = false>
 NX_DEV void kp_group_hashes(const KP_DAG& dag, const FastMod32& items, const uint32_t* l1,
-                            uint32_t st0, uint32_t st1, uint32_t lane, uint32_t (&own)[8]) {
+                            uint32_t st0, uint32_t st1, uint32_t lane, uint32_t (&own)[8],
+                            const uint32_t* seeds = nullptr) {
 #pragma unroll 1
     for (uint32_t h0 = 0; h0 < 16; h0 += KP_HASHES) {
         uint32_t mx[KP_HASHES][32];
 #pragma unroll
         for (int k = 0; k < KP_HASHES; ++k) {
-            const uint32_t s0 = __shfl(st0, (int)(h0 + k), 16);
-            const uint32_t s1 = __shfl(st1, (int)(h0 + k), 16);
+            const uint32_t s0 = SEEDS_IN_LDS ? seeds[h0 + k] : __shfl(st0, (int)(h0 + k), 16);
+            const uint32_t s1 = SEEDS_IN_LDS ? seeds[KP_BLOCK + h0 + k] : __shfl(st1, (int)(h0 + k), 16);
             const uint32_t z = kp_fnv1a(0x811c9dc5u, s0);
             const uint32_t w = kp_fnv1a(z, s1);
             const uint32_t jsr = kp_fnv1a(w, lane);
@@ -357,9 +365,14 @@ NX_DEV void kp_group_hashes(const KP_DAG& dag, const FastMod32& items, const uin
     }
 }
 
+// Seed words parked in LDS across the hash loop of kawpow_search (below). At the tuned shape two
+// workgroups share a CU's 160 KiB: 2 x (65,540 B of L1 + 768 x 5 x 4 B) fits, a sixth word would not.
+#define KP_PARK 5
+
 extern "C" __global__ KP_BOUNDS void kawpow_search(KawpowSearchParams p) {
     __shared__ uint32_t l1[KP_L1_WORDS];
     __shared__ uint32_t stale_word;
+    __shared__ uint32_t park[KP_PARK][KP_BLOCK];
     uint32_t* stale = &stale_word;
     if (blockDim.x != KP_BLOCK) return;  // launched with the wrong block: no shares rather than bad ones
     if (threadIdx.x == 0) {
@@ -378,18 +391,22 @@ extern "C" __global__ KP_BOUNDS void kawpow_search(KawpowSearchParams p) {
     const uint32_t lane = threadIdx.x & 15;
     const uint64_t nonce = p.start_nonce + (uint64_t)blockIdx.x * KP_BLOCK + threadIdx.x;
     uint32_t digest[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    {
-        uint32_t st2[8];
-        kp_seed(p.header, nonce, st2);
-        kp_group_hashes(KP_DAG_HANDLE(p.dag), p.items, l1, st2[0], st2[1], lane, digest);
-    }
     uint32_t st2[8], fin[8];
-    // recomputed: cheaper than 6 VGPRs held across the mix loop. The nonce goes through an empty
-    // asm so the compiler cannot CSE this keccak with the first one (it would keep those results
-    // live across the whole hash loop and spill them).
-    uint32_t nlo = (uint32_t)nonce, nhi = (uint32_t)(nonce >> 32);
-    asm volatile("" : "+v"(nlo), "+v"(nhi));
-    kp_seed(p.header, ((uint64_t)nhi << 32) | nlo, st2);
+    kp_seed(p.header, nonce, st2);
+    // The final absorb needs st2[0..7] again after the hash loop. Words 0..4 wait in LDS, word k of
+    // thread t at park[k][t]: a wave's stores and loads are 64 consecutive dwords (conflict-free).
+    // Words 0 and 1 are also every hash's mix seed, read there by the 16 lanes of the owner's
+    // group, i.e. by the wave that wrote them (LDS serves a wave's accesses in order: no barrier).
+    // Words 5..7 are left to the register allocator.
+#pragma unroll
+    for (int k = 0; k < KP_PARK; ++k) park[k][threadIdx.x] = st2[k];
+    __builtin_amdgcn_wave_barrier();
+    kp_group_hashes<true>(KP_DAG_HANDLE(p.dag), p.items, l1, 0, 0, lane, digest, &park[0][threadIdx.x & ~15u]);
+    // compiler-only fence: without it the parked values may be forwarded from the stores above,
+    // i.e. held in VGPRs (and spilled) across the hash loop
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int k = 0; k < KP_PARK; ++k) st2[k] = park[k][threadIdx.x];
     kp_final(st2, digest, fin);
     const uint64_t head = ((uint64_t)__builtin_bswap32(fin[0]) << 32) | __builtin_bswap32(fin[1]);
     if (head <= p.target) {
