@@ -260,7 +260,9 @@ class ChainState:
         self._check_for_pruning = False
         self.journal_compact_bytes = 64 << 20  # fold coins.log into coins.dat past this size (or the snapshot's)
         self._since_flush = 0
-        self.sig_stats = {"gpu_batches": 0, "gpu_sigs": 0, "host_rechecks": 0}
+        self.gpu_sighash = False              # -gpusighash: legacy SIGHASH_ALL-form message hashes on the GPU too
+        self.sig_stats = {"gpu_batches": 0, "gpu_sigs": 0, "host_rechecks": 0, "gpu_sighashes": 0,
+                          "host_sighashes": 0}
         self.db_format = detect_db_format(datadir, db_format)
         self.coins_db = None
         self._coins_obf = b""
@@ -1213,7 +1215,12 @@ class ChainState:
         par = self.script_threads
         aflags = self.asset_flags(prev)
 
+        gpu_hash = gpu and self.gpu_sighash  # only with the GPU batch: the host path hashes as it verifies
+
         def connect(defer: bool):
+            if defer and gpu_hash:
+                return _core.connect_block(block, height, self.coins, check_scripts, defer, mtp_at, mtp_prev, flags,
+                                           par, self.assets, aflags, idx.hash, defer_sighash=True)
             return _core.connect_block(block, height, self.coins, check_scripts, defer, mtp_at, mtp_prev, flags, par,
                                        self.assets, aflags, idx.hash)
 
@@ -1228,7 +1235,15 @@ class ChainState:
         if gpu and res.num_sigs:
             from ..ops import secp
 
-            verdicts = secp.verify_batch(res.sig_items())
+            if gpu_hash:
+                from ..ops import sighash
+
+                verdicts = sighash.verify_block_sigs(res)
+                self.sig_stats["gpu_sighashes"] += res.num_device_hashes
+                self.sig_stats["host_sighashes"] += res.num_sigs - res.num_device_hashes
+            else:
+                verdicts = secp.verify_batch(res.sig_items())
+                self.sig_stats["host_sighashes"] += len(verdicts)
             self.sig_stats["gpu_batches"] += 1
             self.sig_stats["gpu_sigs"] += len(verdicts)
             for t, i in sorted({res.sig_at[k] for k, v in enumerate(verdicts) if not v}):

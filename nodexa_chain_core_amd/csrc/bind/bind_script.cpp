@@ -2,12 +2,14 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <cstring>
 #include <set>
 
 #include "../chain/coins.hpp"
 #include "../chain/indexes.hpp"
 #include "../chain/interpreter.hpp"
 #include "../chain/sigcache.hpp"
+#include "../chain/sighash.hpp"
 #include "../chain/params.hpp"
 #include "../crypto/secp256k1.hpp"
 #include "../crypto/secp256k1_model32.hpp"
@@ -348,15 +350,73 @@ void bind_script(py::module_& m) {
         .def_readonly("sig_at", &ConnectResult::sig_at)
         .def_property_readonly("asset_undo", [](const ConnectResult& r) { return pyb(r.asset_undo); })
         .def_property_readonly("num_sigs", [](const ConnectResult& r) { return r.sigs.size(); })
+        .def_property_readonly("num_device_hashes", [](const ConnectResult& r) {
+            size_t n = 0;
+            for (auto& p : r.sigs) n += p.device_hash;
+            return n;
+        }, "deferred signatures whose message hash is left to the batch (defer_sighash)")
         .def("sig_items", [](const ConnectResult& r) {
             py::list out;
-            for (auto& p : r.sigs) out.append(py::make_tuple(pyb(p.pubkey), pyb(p.sig), pyb(p.msg.data, 32)));
+            for (size_t k = 0; k < r.sigs.size(); ++k)
+                out.append(py::make_tuple(pyb(r.sigs[k].pubkey), pyb(r.sigs[k].sig), pyb(r.sig_msg(k).data, 32)));
             return out;
-        }, "deferred signatures as (pubkey, DER signature, message) for ops/secp.verify_batch");
+        }, "deferred signatures as (pubkey, DER signature, message) for ops/secp.verify_batch; with defer_sighash "
+           "the messages left to the batch are computed here, on the host")
+        .def("sighash_pack", [](const ConnectResult& r) {
+            SighashPack p;
+            {
+                py::gil_scoped_release rel;
+                p = pack_sighash(r);
+            }
+            return py::make_tuple(pyb(p.arena),
+                                  py::bytes(reinterpret_cast<const char*>(p.jobs.data()), p.jobs.size() * sizeof(SighashJob)),
+                                  py::bytes(reinterpret_cast<const char*>(p.secp_jobs.data()),
+                                            p.secp_jobs.size() * sizeof(SecpVerifyJob)),
+                                  p.device_jobs, p.host_jobs);
+        }, "(arena, SighashJob table, SecpVerifyJob array, device-hashed count, host-hashed count) for "
+           "ops/sighash.verify_block_sigs: the secp records of device-hashed signatures are INVALID with z = 0 until "
+           "sighash_gather_batch fills them");
+    m.attr("SIGHASH_JOB_BYTES") = sizeof(SighashJob);
+    m.attr("SIGHASH_ARENA_SLACK") = SIGHASH_ARENA_SLACK;
+    m.attr("SECP_KIND_INVALID") = SECP_KIND_INVALID;
+    m.def("sighash_template", [](const py::bytes& tx_raw) {
+        const SighashTemplate t(tx_of(tx_raw));
+        return py::make_tuple(pyb(t.bytes), t.script_off);
+    }, "(blanked legacy serialisation, offset of each input's script-length byte)");
+    m.def("sighash_script_code", [](const py::bytes& code) { return pyb(sighash_script_code(bytes_of(code))); },
+          "what SignatureHash writes for the signed input's script: compact size + code without OP_CODESEPARATORs");
+    m.def("sighash_all_form", [](int sigversion, int hash_type) {
+        return sighash_all_form(sigversion ? SigVersion::WITNESS_V0 : SigVersion::BASE, hash_type);
+    }, "whether a signature's message hash can be left to the batch (legacy, SIGHASH_ALL form)");
+    m.def("sighash_check_jobs", [](size_t arena_len, const py::bytes& jobs, py::object n_out) {
+        const std::string j = jobs;
+        if (j.size() % sizeof(SighashJob)) throw std::invalid_argument("job table is not a whole number of records");
+        const size_t n = j.size() / sizeof(SighashJob);
+        std::vector<SighashJob> v(n);
+        std::memcpy(v.data(), j.data(), j.size());
+        sighash_check_jobs(arena_len, v.data(), n, n_out.is_none() ? n : n_out.cast<size_t>());
+    }, py::arg("arena_len"), py::arg("jobs"), py::arg("n_out") = py::none(),
+       "ValueError on a segment outside the arena or an output index >= n_out (default: the job count)");
+    m.def("sighash_gather_model", [](const py::bytes& arena, const py::bytes& jobs) {
+        const std::string j = jobs;
+        if (j.size() % sizeof(SighashJob)) throw std::invalid_argument("job table is not a whole number of records");
+        const size_t n = j.size() / sizeof(SighashJob);
+        std::vector<SighashJob> v(n);
+        std::memcpy(v.data(), j.data(), j.size());
+        const Bytes a = bytes_of(arena);
+        Bytes out;
+        {
+            py::gil_scoped_release rel;
+            out = sighash_gather_model(a, v.data(), n);
+        }
+        return pyb(out);
+    }, "host model of sighash_gather_batch: SHA256d of each job's four arena segments, 32 bytes per job");
     m.def("connect_block", [](const Block& block, int height, CoinsView& view, bool check_scripts, bool defer_sigs,
                               py::object mtp_at, int64_t block_mtp, u32 flags, int threads, assets::State* asset_state,
-                              const assets::Flags& asset_flags, const py::bytes& block_hash, bool sigcache) {
+                              const assets::Flags& asset_flags, const py::bytes& block_hash, bool sigcache,
+                              bool defer_sighash) {
         ConnectOptions opt;
+        opt.defer_sighash = defer_sighash;
         opt.assets = asset_state;
         opt.asset_flags = asset_flags;
         const std::string bh = block_hash;
@@ -385,7 +445,11 @@ void bind_script(py::module_& m) {
        py::arg("defer_sigs") = false, py::arg("mtp_at") = py::none(), py::arg("block_mtp") = 0,
        py::arg("flags") = kBlockScriptFlags, py::arg("threads") = 1, py::arg("assets") = nullptr,
        py::arg("asset_flags") = assets::Flags{}, py::arg("block_hash") = py::bytes(), py::arg("sigcache") = true,
-       "ConnectBlock against the view -> (ConnectResult, serialized CBlockUndo); the view is unchanged on failure");
+       py::arg("defer_sighash") = false,
+       "ConnectBlock against the view -> (ConnectResult, serialized CBlockUndo); the view is unchanged on failure. "
+       "defer_sighash (with defer_sigs only): the legacy SIGHASH_ALL-form message hashes are left to the batch too "
+       "(ConnectResult.sighash_pack); those signatures are not looked up in the signature cache, whose key is the "
+       "message, so their entries age out of the bounded cache instead of being erased on use");
     m.def("disconnect_block", [](const Block& block, const py::bytes& undo, CoinsView& view, assets::State* st,
                                  const py::bytes& asset_undo) {
         const Bytes au = bytes_of(asset_undo);

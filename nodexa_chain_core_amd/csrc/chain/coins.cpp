@@ -620,6 +620,7 @@ ConnectResult connect_block(const Block& block, int height, CoinsView& view, con
         res.dos = dos;
         res.sigs.clear();
         res.sig_at.clear();
+        res.templates.clear();
         return res;
     };
     struct Check {
@@ -632,6 +633,8 @@ ConnectResult connect_block(const Block& block, int height, CoinsView& view, con
     };
     std::vector<Check> checks;
     std::vector<std::unique_ptr<PrecomputedTx>> caches(block.vtx.size());
+    const bool defer_sighash = opt.defer_sigs && opt.defer_sighash;
+    if (defer_sighash) res.templates.resize(block.vtx.size());
     for (size_t t = 0; t < block.vtx.size(); ++t) {
         const Transaction& tx = block.vtx[t];
         const Uint256 txid = tx.txid();
@@ -689,6 +692,7 @@ ConnectResult connect_block(const Block& block, int height, CoinsView& view, con
         if (res.sigop_cost > kMaxBlockSigopsCost) return fail("bad-blk-sigops", 100);
         if (!tx.is_coinbase() && opt.check_scripts) {
             caches[t] = std::make_unique<PrecomputedTx>(tx);
+            if (defer_sighash) res.templates[t] = std::make_shared<const SighashTemplate>(tx);
             for (size_t i = 0; i < tx.vin.size(); ++i)
                 checks.push_back({u32(t), u32(i), spent[i]->out.value, spent[i]->out.script_pubkey});
         }
@@ -727,6 +731,8 @@ ConnectResult connect_block(const Block& block, int height, CoinsView& view, con
         const Transaction& tx = block.vtx[c.t];
         TxSigChecker checker(&tx, c.i, c.value, caches[c.t].get());
         if (opt.defer_sigs) checker.pending = &c.sigs;
+        checker.defer_sighash = defer_sighash;
+        checker.tx_index = c.t;
         if (opt.sigcache) checker.sigcache = TxSigChecker::CacheMode::USE;
         c.ok = verify_script(tx.vin[c.i].script_sig, c.spk, &tx.vin[c.i].witness, opt.script_flags, checker, &c.err);
     };

@@ -20,6 +20,7 @@
 #pragma once
 
 #include <functional>
+#include <memory>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -131,6 +132,11 @@ struct ConnectOptions {
     u32 script_flags = kBlockScriptFlags;
     bool check_scripts = true;
     bool defer_sigs = false;   // collect signatures for a batch verifier instead of checking them
+    // With defer_sigs: also leave the legacy SIGHASH_ALL-form message hashes to the batch
+    // (interpreter.hpp sighash_all_form; chain/sighash.hpp packs them for the GPU). Those
+    // signatures are not looked up in the signature cache, whose key is the message: their entries
+    // age out of the bounded cache instead of being erased on use.
+    bool defer_sighash = false;
     bool sigcache = true;      // skip (and drop) signatures the mempool already verified (sigcache.hpp)
     bool sequence_locks = true;
     // median time past of the block at `height` of this block's chain (BIP68 time locks)
@@ -155,6 +161,13 @@ struct ConnectResult {
     std::vector<PendingSig> sigs;            // with defer_sigs: every signature to verify
     std::vector<std::pair<u32, u32>> sig_at;  // (tx index, input index) of each entry of sigs
     Bytes asset_undo;                          // the asset journal of the block (with opt.assets)
+    // with defer_sighash: the template of every transaction that has a deferred hash, by block index
+    std::vector<std::shared_ptr<const SighashTemplate>> templates;
+    // The message of sigs[k]: stored, or computed here on the host for a deferred hash.
+    Uint256 sig_msg(size_t k) const {
+        const PendingSig& p = sigs[k];
+        return p.device_hash ? sighash_from_template(*templates[p.tx_index], p.n_in, p.code, p.hash_type) : p.msg;
+    }
 };
 
 // Applies `block` (at `height`) to `view`; on failure the view is left unchanged.

@@ -325,6 +325,64 @@ PrecomputedTx::PrecomputedTx(const Transaction& tx) {
     ready = true;
 }
 
+// CTransactionSignatureSerializer::SerializeScriptCode: the script without OP_CODESEPARATORs.
+// As in the reference, the length prefix is size - separators and the bytes stop where the op
+// walk stops (a truncated push ends the walk early, so the prefix can overstate the bytes).
+static void write_script_code(Writer& w, const Bytes& script_code) {
+    size_t pc = 0, seps = 0;
+    u8 op;
+    while (script_get_op(script_code, pc, op, nullptr))
+        if (op == kOP_CODESEPARATOR) ++seps;
+    w.compact_size(script_code.size() - seps);
+    size_t seg = 0;
+    pc = 0;
+    while (script_get_op(script_code, pc, op, nullptr)) {
+        if (op == kOP_CODESEPARATOR) {
+            w.raw(script_code.data() + seg, pc - 1 - seg);
+            seg = pc;
+        }
+    }
+    if (seg != script_code.size()) w.raw(script_code.data() + seg, pc - seg);
+}
+
+Bytes sighash_script_code(const Bytes& script_code) {
+    Writer w;
+    write_script_code(w, script_code);
+    return std::move(w.buf);
+}
+
+SighashTemplate::SighashTemplate(const Transaction& tx) {
+    Writer w;
+    w.i32_(tx.version);
+    w.compact_size(tx.vin.size());
+    script_off.reserve(tx.vin.size());
+    for (auto& in : tx.vin) {
+        w.u256(in.prevout.hash);
+        w.u32_(in.prevout.n);
+        script_off.push_back(u32(w.buf.size()));
+        w.compact_size(0);
+        w.u32_(in.sequence);
+    }
+    w.compact_size(tx.vout.size());
+    for (auto& o : tx.vout) {
+        w.i64_(o.value);
+        w.var_bytes(o.script_pubkey);
+    }
+    w.u32_(tx.lock_time);
+    bytes = std::move(w.buf);
+}
+
+Uint256 sighash_from_template(const SighashTemplate& t, unsigned n_in, const Bytes& emitted_code, int32_t hash_type) {
+    const size_t off = t.script_off.at(n_in);
+    Writer w;
+    w.buf.reserve(t.bytes.size() + emitted_code.size() + 4);
+    w.raw(t.bytes.data(), off);
+    w.raw(emitted_code);
+    w.raw(t.bytes.data() + off + 1, t.bytes.size() - off - 1);
+    w.i32_(hash_type);
+    return hash_bytes(w.buf);
+}
+
 Uint256 signature_hash(const Bytes& script_code, const Transaction& tx, unsigned n_in, int hash_type, Amount amount,
                        SigVersion sigversion, const PrecomputedTx* cache) {
     const int base = hash_type & 0x1f;
@@ -364,25 +422,6 @@ Uint256 signature_hash(const Bytes& script_code, const Transaction& tx, unsigned
     one.data[0] = 1;
     if (n_in >= tx.vin.size()) return one;
     if (base == SIGHASH_SINGLE && n_in >= tx.vout.size()) return one;
-    // CTransactionSignatureSerializer::SerializeScriptCode: the script without OP_CODESEPARATORs.
-    // As in the reference, the length prefix is size - separators and the bytes stop where the op
-    // walk stops (a truncated push ends the walk early, so the prefix can overstate the bytes).
-    auto write_code = [&](Writer& w) {
-        size_t pc = 0, seps = 0;
-        u8 op;
-        while (script_get_op(script_code, pc, op, nullptr))
-            if (op == kOP_CODESEPARATOR) ++seps;
-        w.compact_size(script_code.size() - seps);
-        size_t seg = 0;
-        pc = 0;
-        while (script_get_op(script_code, pc, op, nullptr)) {
-            if (op == kOP_CODESEPARATOR) {
-                w.raw(script_code.data() + seg, pc - 1 - seg);
-                seg = pc;
-            }
-        }
-        if (seg != script_code.size()) w.raw(script_code.data() + seg, pc - seg);
-    };
     Writer w;
     w.i32_(tx.version);
     const size_t nin = anyone ? 1 : tx.vin.size();
@@ -392,7 +431,7 @@ Uint256 signature_hash(const Bytes& script_code, const Transaction& tx, unsigned
         w.u256(tx.vin[i].prevout.hash);
         w.u32_(tx.vin[i].prevout.n);
         if (i != n_in) w.compact_size(0);
-        else write_code(w);
+        else write_script_code(w, script_code);
         if (i != n_in && (base == SIGHASH_SINGLE || base == SIGHASH_NONE)) w.u32_(0);
         else w.u32_(tx.vin[i].sequence);
     }
@@ -421,6 +460,16 @@ bool TxSigChecker::check_sig(const Bytes& sig_in, const Bytes& pubkey, const Byt
     if (sig_in.empty()) return false;
     const int hash_type = sig_in.back();
     const Bytes sig(sig_in.begin(), sig_in.end() - 1);
+    if (pending && defer_sighash && sighash_all_form(sv, hash_type) && n_in_ < tx_->vin.size()) {
+        PendingSig p{Uint256(), sig, pubkey};
+        p.device_hash = true;
+        p.tx_index = tx_index;
+        p.n_in = n_in_;
+        p.hash_type = hash_type;
+        p.code = sighash_script_code(script_code);
+        pending->push_back(std::move(p));
+        return true;
+    }
     const Uint256 msg = signature_hash(script_code, *tx_, n_in_, hash_type, amount_, sv, cache_);
     if (sigcache != CacheMode::NONE && SigCache::instance().get(msg.data, pubkey, sig, sigcache == CacheMode::USE))
         return true;  // verified when the transaction entered the mempool

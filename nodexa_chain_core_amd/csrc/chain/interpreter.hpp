@@ -94,6 +94,32 @@ struct PrecomputedTx {
 Uint256 signature_hash(const Bytes& script_code, const Transaction& tx, unsigned n_in, int hash_type, Amount amount,
                        SigVersion sigversion, const PrecomputedTx* cache = nullptr);
 
+// The legacy (SigVersion::BASE) message hash in its SIGHASH_ALL form, split so that a batch can
+// compute it elsewhere (ops/sighash, hip/kernels/sighash.hip): one template per transaction, and
+// per signature only the script code bytes and the hash type.
+// The template is the legacy serialisation with every input script empty (version, compact size
+// of vin, 41 bytes per input, outputs, locktime); script_off[i] is the offset of input i's
+// script-length byte (a single 0x00). The preimage of input i is
+//   T[0:off_i] | sighash_script_code(code) | T[off_i+1:] | hash type as LE int32.
+struct SighashTemplate {
+    Bytes bytes;
+    std::vector<u32> script_off;
+    SighashTemplate() = default;
+    explicit SighashTemplate(const Transaction& tx);
+};
+// What signature_hash writes for the signed input's script: compact size, then the code with its
+// OP_CODESEPARATORs removed (with the reference's quirks: see signature_hash).
+Bytes sighash_script_code(const Bytes& script_code);
+// True for the signatures whose legacy hash has the SIGHASH_ALL form: no ANYONECANPAY, and a base
+// type that is neither NONE nor SINGLE (so also the odd types 0x00, 0x04, 0x21 ..., which the
+// reference hashes as ALL with the literal type appended).
+inline bool sighash_all_form(SigVersion sv, int hash_type) {
+    const int base = hash_type & 0x1f;
+    return sv == SigVersion::BASE && !(hash_type & 0x80) && base != 2 && base != 3;
+}
+// SHA256d of the preimage above: equals signature_hash for every sighash_all_form signature.
+Uint256 sighash_from_template(const SighashTemplate& t, unsigned n_in, const Bytes& emitted_code, int32_t hash_type);
+
 // Signature / locktime oracle used by EvalScript.
 class SigChecker {
 public:
@@ -112,6 +138,13 @@ struct PendingSig {
     Uint256 msg;
     Bytes sig;
     Bytes pubkey;
+    // With defer_sighash, a sighash_all_form signature leaves `msg` unset and carries what the
+    // batch needs to compute it: its place in the block, the full hash type and the emitted
+    // script code (sighash_script_code).
+    bool device_hash = false;
+    u32 tx_index = 0, n_in = 0;
+    int32_t hash_type = 0;
+    Bytes code;
 };
 
 class TxSigChecker : public SigChecker {
@@ -126,6 +159,10 @@ public:
     // valid for scripts whose outcome cannot depend on a signature failing, i.e. for blocks,
     // where any failing signature invalidates the block anyway.
     std::vector<PendingSig>* pending = nullptr;
+    // With `pending`: leave the message hash of sighash_all_form signatures to the batch too.
+    // Those signatures are not looked up in the signature cache (its key is the message).
+    bool defer_sighash = false;
+    u32 tx_index = 0;  // the transaction's index in its block, recorded in deferred hashes
     // Signature cache (sigcache.hpp): STORE remembers every signature that verifies (mempool
     // acceptance); USE answers from the cache first and erases what it hits (block validation,
     // CachingTransactionSignatureChecker with store = false).

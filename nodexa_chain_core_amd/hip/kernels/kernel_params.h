@@ -146,6 +146,27 @@ struct SecpVerifyParams {
     uint32_t pad;
 };
 
+// Gathered SHA-256d for legacy signature hashes (sighash.hip sighash_gather_batch): one job per
+// signature. The message is the concatenation of four byte ranges of one shared arena (any of
+// them may be empty): the transaction's blanked template up to the input's script-length byte,
+// the script code, the rest of the template, the hash type (csrc/chain/sighash.hpp).
+#define SIGHASH_SEGMENTS 4
+#define SIGHASH_ARENA_SLACK 8u  // readable bytes the host keeps after the arena: the kernel reads whole aligned dwords
+struct SighashJob {
+    uint32_t off[SIGHASH_SEGMENTS];  // byte offsets into the arena
+    uint32_t len[SIGHASH_SEGMENTS];
+    uint32_t out_index;              // row of `digests` / entry of `secp_jobs` this job fills
+    uint32_t kind;                   // the signature's real SECP_KIND_*, written together with z
+};
+struct SighashParams {
+    const uint8_t* arena;
+    const struct SighashJob* jobs;
+    uint8_t* digests;                // nullable: out_index x 32 raw digest bytes
+    struct SecpVerifyJob* secp_jobs; // nullable: z and kind of entry out_index are written
+    uint32_t n;
+    uint32_t pad;
+};
+
 // Batch verification of packed Equihash(200,9) solutions (equihash.hip eq_verify).
 #define EQ_SOL_WORDS 336  // 1344 bytes = 512 x 21-bit big-endian indices
 struct EquihashVerifyParams {

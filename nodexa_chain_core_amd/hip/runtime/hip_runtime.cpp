@@ -618,6 +618,26 @@ PYBIND11_MODULE(_hip, m) {
         k.launch_bytes(dim3((n + 255) / 256), dim3(256), 0, as_stream(stream), &p, sizeof(p));
     });
 
+    // ---- gathered SHA-256d of legacy signature hashes (sighash.hip): n SighashJob records over one
+    // arena -> raw digests and / or the z limbs and kind of the secp jobs (either pointer may be 0).
+    // The caller has validated the table (_core.sighash_check_jobs) and keeps SIGHASH_ARENA_SLACK
+    // readable bytes after the arena.
+    m.attr("SIGHASH_JOB_BYTES") = sizeof(SighashJob);
+    m.attr("SIGHASH_ARENA_SLACK") = SIGHASH_ARENA_SLACK;
+    m.def("launch_sighash_gather", [](const Kernel& k, uintptr_t arena, uintptr_t jobs, uint32_t n, uintptr_t digests,
+                                      uintptr_t secp_jobs, uintptr_t stream) {
+        if (n == 0) return;
+        if (!arena || !jobs) throw std::invalid_argument("sighash: null arena or job table");
+        if (!digests && !secp_jobs) throw std::invalid_argument("sighash: no output requested");
+        SighashParams p{};
+        p.arena = reinterpret_cast<const uint8_t*>(arena);
+        p.jobs = reinterpret_cast<const SighashJob*>(jobs);
+        p.digests = reinterpret_cast<uint8_t*>(digests);
+        p.secp_jobs = reinterpret_cast<SecpVerifyJob*>(secp_jobs);
+        p.n = n;
+        k.launch_bytes(dim3((n + 255) / 256), dim3(256), 0, as_stream(stream), &p, sizeof(p));
+    });
+
     // ---- Equihash(200,9): one full Wagner solve for `num_inst` inputs, enqueued on `stream`
     m.attr("EQ_BUCKETS") = EQ_BUCKETS;
     m.attr("EQ_WORDS") = EQ_WORDS;

@@ -319,6 +319,9 @@ class Node:
         cores = os.cpu_count() or 1
         self.state.script_threads = max(1, min(16, cores + par if par <= 0 else par))
         self.state.gpu_signatures = a.get("gpusigs", "auto")  # -gpusigs=auto|on|off: GPU batch ECDSA in blocks
+        # -gpusighash=0|1: with the GPU batch, also compute the legacy SIGHASH_ALL-form message hashes on
+        # the GPU (ops/sighash); without a GPU batch it has nothing to act on
+        self.state.gpu_sighash = a.get_bool("gpusighash", False)
         if self.datadir is not None:  # fee_estimates.dat (src/init.cpp: est_filein), before the mempool
             self.state.load_fee_estimates(os.path.join(self.datadir, "fee_estimates.dat"))
         if self.datadir is not None and a.get_bool("persistmempool", True):  # -persistmempool (LoadMempool)
@@ -922,6 +925,8 @@ class Node:
         for g in out:
             g["intensity"] = svc.window
             g["ranks"] = svc.world_size
+        if out:  # the node's own entry: block validation's GPU batches (-gpusigs, -gpusighash)
+            out[0]["block_sigs"] = dict(self.state.sig_stats)
         if out and self.gpus:
             try:
                 from .ops import runtime

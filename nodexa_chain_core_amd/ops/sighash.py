@@ -1,0 +1,110 @@
+"""Legacy signature hashes on the GPU (hip/kernels/sighash.hip), feeding the batch ECDSA verifier.
+
+The reference computes SignatureHash (src/script/interpreter.cpp) on the host once per signature;
+for a legacy input that re-serialises and double-SHA-256es the whole transaction, so a transaction
+with many inputs costs quadratic work before a single signature is checked. With
+`connect_block(defer_sigs=True, defer_sighash=True)` the native core leaves those hashes out and
+`ConnectResult.sighash_pack()` lays the block out as one arena (one blanked template per
+transaction, one script code and hash type per signature) plus a job table of four (offset, length)
+segments per signature. `sighash_gather_batch` hashes one job per lane and writes the digest
+straight into the `z` limbs of the packed secp job, whose `kind` it sets in the same pass:
+the records are uploaded INVALID, so a signature the kernel never reached can only fail.
+
+`digests` is the kernel on its own; `verify_block_sigs` is the block path: gather, then
+`secp_verify_batch` on the same stream, verdicts only coming back.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from .. import _core
+from ..utils.trace import traced
+from . import runtime, secp
+
+JOB_BYTES = _core.SIGHASH_JOB_BYTES
+
+
+def _upload_arena(arena: bytes, dev: torch.device) -> torch.Tensor:
+    """The arena on the device, followed by the zeroed slack the kernel's aligned dword reads may touch."""
+    buf = bytearray(arena)
+    buf += bytes((-len(buf)) % 4 + _core.SIGHASH_ARENA_SLACK)
+    return torch.frombuffer(buf, dtype=torch.uint8).to(dev)
+
+
+def _upload_jobs(arena: bytes, jobs: bytes, n_out: int, dev: torch.device):
+    # nothing malformed reaches the device: every segment inside the arena, every output in range
+    _core.sighash_check_jobs(len(arena), jobs, n_out)
+    return _upload_arena(arena, dev), torch.frombuffer(bytearray(jobs), dtype=torch.int32).to(dev)
+
+
+def _device(device: int | None) -> torch.device:
+    return torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
+
+
+def digests(arena: bytes, jobs: bytes, device: int | None = None) -> np.ndarray:
+    """(n, 32) uint8: SHA256d of each job's four arena segments, row = the job's output index
+    (which must be below the job count). Equals `_core.sighash_gather_model` row for row when the
+    output indices are 0..n-1."""
+    n = len(jobs) // JOB_BYTES
+    if n == 0:
+        return np.zeros((0, 32), np.uint8)
+    runtime.require_gpu()
+    dev = _device(device)
+    with torch.cuda.device(dev):
+        d_arena, d_jobs = _upload_jobs(arena, jobs, n, dev)
+        out = torch.zeros((n, 32), dtype=torch.uint8, device=dev)
+        runtime.hip().launch_sighash_gather(runtime.static_kernel("sighash", "sighash_gather_batch"),
+                                            d_arena.data_ptr(), d_jobs.data_ptr(), n, out.data_ptr(), 0,
+                                            runtime.current_stream_handle())
+        return out.cpu().numpy()
+
+
+def gather_into_secp(arena: bytes, jobs: bytes, secp_jobs: bytes, device: int | None = None) -> bytes:
+    """Run the gather over a packed SecpVerifyJob array and return the array as the device holds it
+    afterwards: the records the job table names carry their z limbs and real kind, all others are
+    untouched."""
+    n = len(jobs) // JOB_BYTES
+    n_secp = len(secp_jobs) // _core.SECP_JOB_BYTES
+    if n == 0:
+        return bytes(secp_jobs)
+    runtime.require_gpu()
+    dev = _device(device)
+    with torch.cuda.device(dev):
+        d_arena, d_jobs = _upload_jobs(arena, jobs, n_secp, dev)
+        d_secp = torch.frombuffer(bytearray(secp_jobs), dtype=torch.int32).to(dev)
+        runtime.hip().launch_sighash_gather(runtime.static_kernel("sighash", "sighash_gather_batch"),
+                                            d_arena.data_ptr(), d_jobs.data_ptr(), n, 0, d_secp.data_ptr(),
+                                            runtime.current_stream_handle())
+        return d_secp.cpu().numpy().tobytes()
+
+
+@traced("sighash.verify_block_sigs")
+def verify_block_sigs(res, device: int | None = None) -> list[bool]:
+    """CPubKey::Verify's answer for every deferred signature of a `connect_block(defer_sigs=True,
+    defer_sighash=True)` result, in the order of `res.sig_items()`. The message hashes left to the
+    batch are computed on the device and never come back; only the verdicts do. A verdict 2
+    (degenerate addition) is re-checked on the host with the host-computed message."""
+    n = res.num_sigs
+    if n == 0:
+        return []
+    runtime.require_gpu()
+    h = runtime.hip()
+    dev = _device(device)
+    arena, jobs, secp_jobs, n_dev, _n_host = res.sighash_pack()
+    with torch.cuda.device(dev):
+        stream = runtime.current_stream_handle()
+        d_secp = torch.frombuffer(bytearray(secp_jobs), dtype=torch.int32).to(dev)
+        out = torch.empty(n, dtype=torch.int32, device=dev)
+        gtab = secp._gen_table(dev)  # uploaded on first use: before the launches, not between them
+        if n_dev:
+            d_arena, d_jobs = _upload_jobs(arena, jobs, n, dev)
+            h.launch_sighash_gather(runtime.static_kernel("sighash", "sighash_gather_batch"), d_arena.data_ptr(),
+                                    d_jobs.data_ptr(), n_dev, 0, d_secp.data_ptr(), stream)
+        h.launch_secp_verify(runtime.static_kernel("secp256k1_verify", "secp_verify_batch"), d_secp.data_ptr(), n,
+                             gtab.data_ptr(), out.data_ptr(), stream)
+        verdicts = out.cpu().tolist()
+    if 2 in verdicts:
+        items = res.sig_items()
+        return [bool(_core.secp_verify(*items[k])) if v == 2 else v == 1 for k, v in enumerate(verdicts)]
+    return [v == 1 for v in verdicts]
