@@ -13,6 +13,7 @@
 #include "../chain/params.hpp"
 #include "../crypto/secp256k1.hpp"
 #include "../crypto/secp256k1_model32.hpp"
+#include "../../hip/kernels/secp256k1_probe.hpp"
 
 namespace py = pybind11;
 using namespace nodexa;
@@ -167,6 +168,20 @@ void bind_script(py::module_& m) {
                               sg.size(), reinterpret_cast<const u8*>(m32.data()), job);
         return secp::verify_job_model32(job);
     }, "the GPU verifier's 32-bit-limb arithmetic run on the host: 1 valid, 0 invalid, 2 degenerate");
+    m.attr("SECP_PROBE_IN_BYTES") = SECP_PROBE_IN_WORDS * 4;
+    m.attr("SECP_PROBE_OUT_BYTES") = SECP_PROBE_OUT_WORDS * 4;
+    m.def("secp32_probe", [](uint32_t op, const py::bytes& records) {
+        const std::string in = records;
+        if (op >= SECP_PROBE_NUM_OPS) throw std::invalid_argument("secp32_probe: unknown op");
+        if (in.size() % (SECP_PROBE_IN_WORDS * 4)) throw std::invalid_argument("secp32_probe: ragged records");
+        const size_t n = in.size() / (SECP_PROBE_IN_WORDS * 4);
+        std::vector<uint32_t> w(n * SECP_PROBE_IN_WORDS), out(n * SECP_PROBE_OUT_WORDS);
+        std::memcpy(w.data(), in.data(), in.size());
+        for (size_t i = 0; i < n; ++i)
+            secp32::probe_record(op, w.data() + i * SECP_PROBE_IN_WORDS, out.data() + i * SECP_PROBE_OUT_WORDS);
+        return py::bytes(reinterpret_cast<const char*>(out.data()), out.size() * 4);
+    }, "one primitive of the GPU verifier's limb arithmetic over packed records, run on the host "
+       "(hip/kernels/secp256k1_probe.hpp; the secp_probe kernel runs the same switch on the device)");
 
     // ---------------------------------------------------------------- interpreter
     m.attr("SCRIPT_VERIFY_P2SH") = u32(SCRIPT_VERIFY_P2SH);

@@ -75,28 +75,8 @@ const uint32_t* gen_table32() {
 }
 
 int verify_job_model32(const SecpVerifyJob& job) {
-    using namespace secp32;
-    if (job.kind != SECP_KIND_UNCOMPRESSED && job.kind != SECP_KIND_EVEN && job.kind != SECP_KIND_ODD) return 0;
-    A q;
-    F r, s, z;
-    for (int i = 0; i < 8; ++i) {
-        q.x.v[i] = job.x[i];
-        q.y.v[i] = job.y[i];
-        r.v[i] = job.r[i];
-        s.v[i] = job.s[i];
-        z.v[i] = job.z[i];
-    }
-    if (s_geq_n(z)) s_sub_n(z);
-    const F rhs = f_add(f_mul(f_sqr(q.x), q.x), f_mul_small(f_one(), 7));
-    if (job.kind == SECP_KIND_UNCOMPRESSED) {
-        if (f_geq_p(q.x) || f_geq_p(q.y) || !f_eq(f_sqr(q.y), rhs)) return 0;
-    } else {
-        F y;
-        if (f_geq_p(q.x) || !f_sqrt(rhs, y)) return 0;
-        if ((y.v[0] & 1u) != (job.kind & 1u)) y = f_sub(f_zero(), y);
-        q.y = y;
-    }
-    return ecdsa_verify32(q, r, s, z, reinterpret_cast<const A*>(gen_table32()));
+    // the kernel's own body (secp256k1_device.hpp verify_job32), not a copy of it
+    return int(secp32::verify_job32(job, reinterpret_cast<const secp32::A*>(gen_table32())));
 }
 
 }  // namespace nodexa::secp

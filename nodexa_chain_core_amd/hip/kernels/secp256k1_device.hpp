@@ -13,6 +13,8 @@
 
 #include <stdint.h>
 
+#include "kernel_params.h"
+
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define SECP_HD __host__ __device__ __forceinline__
@@ -432,6 +434,38 @@ SECP_HD int ecdsa_verify32(const A& q, const F& r, const F& s, const F& z, const
         c >>= 32;
     }
     return f_eq(f_mul(rn, zz2), acc.x) ? 1 : 0;
+}
+
+// One packed job (kernel_params.h SecpVerifyJob), the whole body of secp_verify_batch: load the
+// limbs, reduce z, check or decompress the key, verify. The kernel and the host model
+// (csrc/crypto/secp256k1_model32.cpp) both call this, so the host tests run the kernel's own text.
+SECP_HD uint32_t verify_job32(const SecpVerifyJob& job, const A* gtab) {
+    const uint32_t kind = job.kind;
+    uint32_t result = 0;
+    if (kind == SECP_KIND_UNCOMPRESSED || kind == SECP_KIND_EVEN || kind == SECP_KIND_ODD) {
+        A q;
+        F r, s, z;
+        for (int i = 0; i < 8; ++i) {
+            q.x.v[i] = job.x[i];
+            q.y.v[i] = job.y[i];
+            r.v[i] = job.r[i];
+            s.v[i] = job.s[i];
+            z.v[i] = job.z[i];
+        }
+        if (s_geq_n(z)) s_sub_n(z);
+        const F rhs = f_add(f_mul(f_sqr(q.x), q.x), f_mul_small(f_one(), 7));
+        bool ok;
+        if (kind == SECP_KIND_UNCOMPRESSED) {
+            ok = !f_geq_p(q.x) && !f_geq_p(q.y) && f_eq(f_sqr(q.y), rhs);
+        } else {
+            F y;
+            ok = !f_geq_p(q.x) && f_sqrt(rhs, y);
+            if ((y.v[0] & 1u) != (kind & 1u)) y = f_sub(f_zero(), y);
+            q.y = y;
+        }
+        if (ok) result = (uint32_t)ecdsa_verify32(q, r, s, z, gtab);
+    }
+    return result;
 }
 
 }  // namespace secp32

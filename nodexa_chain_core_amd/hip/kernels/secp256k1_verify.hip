@@ -16,31 +16,5 @@ using namespace secp32;
 extern "C" __global__ __launch_bounds__(256) void secp_verify_batch(SecpVerifyParams p) {
     const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
     if (idx >= p.n) return;
-    const SecpVerifyJob& job = p.jobs[idx];
-    const uint32_t kind = job.kind;
-    uint32_t result = 0;
-    if (kind == SECP_KIND_UNCOMPRESSED || kind == SECP_KIND_EVEN || kind == SECP_KIND_ODD) {
-        A q;
-        F r, s, z;
-        for (int i = 0; i < 8; ++i) {
-            q.x.v[i] = job.x[i];
-            q.y.v[i] = job.y[i];
-            r.v[i] = job.r[i];
-            s.v[i] = job.s[i];
-            z.v[i] = job.z[i];
-        }
-        if (s_geq_n(z)) s_sub_n(z);
-        const F rhs = f_add(f_mul(f_sqr(q.x), q.x), f_mul_small(f_one(), 7));
-        bool ok;
-        if (kind == SECP_KIND_UNCOMPRESSED) {
-            ok = !f_geq_p(q.x) && !f_geq_p(q.y) && f_eq(f_sqr(q.y), rhs);
-        } else {
-            F y;
-            ok = !f_geq_p(q.x) && f_sqrt(rhs, y);
-            if ((y.v[0] & 1u) != (kind & 1u)) y = f_sub(f_zero(), y);
-            q.y = y;
-        }
-        if (ok) result = (uint32_t)ecdsa_verify32(q, r, s, z, (const A*)p.gtab);
-    }
-    p.out[idx] = result;
+    p.out[idx] = verify_job32(p.jobs[idx], (const A*)p.gtab);  // secp256k1_device.hpp, shared with the host model
 }

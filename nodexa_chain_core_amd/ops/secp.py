@@ -31,10 +31,9 @@ def _gen_table(dev: torch.device) -> torch.Tensor:
         return t
 
 
-@traced("secp.verify_batch")
-def verify_batch(items: list[tuple[bytes, bytes, bytes]], device: int | None = None) -> list[bool]:
-    """items: (public key, DER signature without the hash-type byte, 32-byte message).
-    Returns CPubKey::Verify's answer for each (lax DER, high S accepted)."""
+def verify_batch_raw(items: list[tuple[bytes, bytes, bytes]], device: int | None = None) -> list[int]:
+    """The kernel's own verdict for each item of `verify_batch`: 1 valid, 0 invalid, 2 "an addition
+    met a doubling / inverse case, ask the host". Nothing is re-checked here."""
     if not items:
         return []
     runtime.require_gpu()
@@ -47,9 +46,15 @@ def verify_batch(items: list[tuple[bytes, bytes, bytes]], device: int | None = N
         out = torch.empty(len(items), dtype=torch.int32, device=dev)
         h.launch_secp_verify(kern, jobs.data_ptr(), len(items), _gen_table(dev).data_ptr(), out.data_ptr(),
                              runtime.current_stream_handle())
-        verdicts = out.cpu().tolist()
+        return out.cpu().tolist()
+
+
+@traced("secp.verify_batch")
+def verify_batch(items: list[tuple[bytes, bytes, bytes]], device: int | None = None) -> list[bool]:
+    """items: (public key, DER signature without the hash-type byte, 32-byte message).
+    Returns CPubKey::Verify's answer for each (lax DER, high S accepted)."""
     res = []
-    for (pub, sig, msg), v in zip(items, verdicts):
+    for (pub, sig, msg), v in zip(items, verify_batch_raw(items, device)):
         if v == 2:  # a doubling / inverse case inside an addition: the host decides
             res.append(bool(_core.secp_verify(pub, sig, msg)))
         else:

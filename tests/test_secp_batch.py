@@ -51,9 +51,10 @@ def test_model32_matches_golden(core):
     assert any(e for *_, e in cs) and not all(e for *_, e in cs)
     for pub, sig, m, expect in cs:
         v = core.secp_verify_model32(pub, sig, m)
-        assert v in (0, 1, 2)
-        if v != 2:
-            assert (v == 1) == expect, (pub.hex(), sig.hex(), m.hex())
+        # never 2 ("ask the host") on random input: that verdict belongs to the constructed
+        # doubling / inverse cases of test_secp_edges.py alone
+        assert v in (0, 1)
+        assert (v == 1) == expect, (pub.hex(), sig.hex(), m.hex())
 
 
 def test_pack_jobs_layout(core):
@@ -67,5 +68,8 @@ def test_gpu_batch_verify_matches_golden(core, gpu):
     from nodexa_chain_core_amd.ops import secp
 
     cs = cases(core, 1000, seed=5)
-    got = secp.verify_batch([(p, s, m) for p, s, m, _ in cs], device=0)
-    assert got == [e for *_, e in cs]
+    items = [(p, s, m) for p, s, m, _ in cs]
+    raw = secp.verify_batch_raw(items, device=0)
+    assert set(raw) <= {0, 1}  # the kernel's own verdicts: none of them left to the host
+    assert [v == 1 for v in raw] == [e for *_, e in cs]
+    assert secp.verify_batch(items, device=0) == [e for *_, e in cs]
