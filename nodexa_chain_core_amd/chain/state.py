@@ -261,8 +261,11 @@ class ChainState:
         self.journal_compact_bytes = 64 << 20  # fold coins.log into coins.dat past this size (or the snapshot's)
         self._since_flush = 0
         self.gpu_sighash = False              # -gpusighash: legacy SIGHASH_ALL-form message hashes on the GPU too
+        self.gpu_sighash_forms = "legacy-all"  # "all" with -gpusighash=2: every form, witness v0 included
+        # gpu_sighashes_v0 / gpu_sighashes_partial: of gpu_sighashes, the witness-v0 hashes and the
+        # legacy hashes of another form than ALL's (both only with -gpusighash=2)
         self.sig_stats = {"gpu_batches": 0, "gpu_sigs": 0, "host_rechecks": 0, "gpu_sighashes": 0,
-                          "host_sighashes": 0}
+                          "host_sighashes": 0, "gpu_sighashes_v0": 0, "gpu_sighashes_partial": 0}
         self.db_format = detect_db_format(datadir, db_format)
         self.coins_db = None
         self._coins_obf = b""
@@ -1220,7 +1223,8 @@ class ChainState:
         def connect(defer: bool):
             if defer and gpu_hash:
                 return _core.connect_block(block, height, self.coins, check_scripts, defer, mtp_at, mtp_prev, flags,
-                                           par, self.assets, aflags, idx.hash, defer_sighash=True)
+                                           par, self.assets, aflags, idx.hash, defer_sighash=True,
+                                           defer_all_forms=self.gpu_sighash_forms == "all")
             return _core.connect_block(block, height, self.coins, check_scripts, defer, mtp_at, mtp_prev, flags, par,
                                        self.assets, aflags, idx.hash)
 
@@ -1241,6 +1245,8 @@ class ChainState:
                 verdicts = sighash.verify_block_sigs(res)
                 self.sig_stats["gpu_sighashes"] += res.num_device_hashes
                 self.sig_stats["host_sighashes"] += res.num_sigs - res.num_device_hashes
+                self.sig_stats["gpu_sighashes_v0"] += res.num_device_v0
+                self.sig_stats["gpu_sighashes_partial"] += res.num_device_partial
             else:
                 verdicts = secp.verify_batch(res.sig_items())
                 self.sig_stats["host_sighashes"] += len(verdicts)

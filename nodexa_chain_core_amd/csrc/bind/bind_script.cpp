@@ -3,7 +3,9 @@
 #include <pybind11/stl.h>
 
 #include <cstring>
+#include <map>
 #include <set>
+#include <tuple>
 
 #include "../chain/coins.hpp"
 #include "../chain/indexes.hpp"
@@ -356,8 +358,8 @@ void bind_script(py::module_& m) {
             return out;
         }, py::arg("hashes") = py::none(),
            "unspent asset outputs to these hash160s (all when None): (txid, n, value, spk, height, coinbase)");
-    py::class_<ConnectResult>(m, "ConnectResult")
-        .def_readonly("ok", &ConnectResult::ok)
+    py::class_<ConnectResult> cr(m, "ConnectResult");
+    cr.def_readonly("ok", &ConnectResult::ok)
         .def_readonly("reject", &ConnectResult::reject)
         .def_readonly("dos", &ConnectResult::dos)
         .def_readonly("fees", &ConnectResult::fees)
@@ -391,7 +393,111 @@ void bind_script(py::module_& m) {
         }, "(arena, SighashJob table, SecpVerifyJob array, device-hashed count, host-hashed count) for "
            "ops/sighash.verify_block_sigs: the secp records of device-hashed signatures are INVALID with z = 0 until "
            "sighash_gather_batch fills them");
+    cr.def_readonly("all_forms", &ConnectResult::all_forms, "connected with defer_all_forms")
+        .def_property_readonly("num_device_v0", [](const ConnectResult& r) {
+            size_t n = 0;
+            for (auto& p : r.sigs) n += p.device_hash && p.sigversion == SigVersion::WITNESS_V0;
+            return n;
+        }, "of num_device_hashes: witness-v0 signatures (defer_all_forms)")
+        .def_property_readonly("num_device_partial", [](const ConnectResult& r) {
+            size_t n = 0;
+            for (auto& p : r.sigs)
+                n += p.device_hash && p.sigversion == SigVersion::BASE && !sighash_all_form(SigVersion::BASE, p.hash_type);
+            return n;
+        }, "of num_device_hashes: legacy signatures of another form than ALL's (defer_all_forms)")
+        .def("sighash_pack_var", [](const ConnectResult& r) {
+            SighashVarPack p;
+            {
+                py::gil_scoped_release rel;
+                p = pack_sighash_var(r);
+            }
+            return py::make_tuple(pyb(p.arena),
+                                  py::bytes(reinterpret_cast<const char*>(p.segs.data()), p.segs.size() * sizeof(SighashSeg)),
+                                  py::bytes(reinterpret_cast<const char*>(p.jobs.data()), p.jobs.size() * sizeof(SighashVarJob)),
+                                  py::bytes(reinterpret_cast<const char*>(p.secp_jobs.data()),
+                                            p.secp_jobs.size() * sizeof(SecpVerifyJob)),
+                                  p.device_jobs, p.host_jobs);
+        }, "(arena, SighashSeg table, SighashVarJob table, SecpVerifyJob array, device-hashed count, host-hashed count) "
+           "of a defer_all_forms result, for ops/sighash.verify_block_sigs: the secp records of device-hashed "
+           "signatures are INVALID with z = 0 until sighash_gather_var fills them");
+    m.def("sighash_pack_var_cases", [](const std::vector<std::tuple<py::bytes, unsigned, py::bytes, int, Amount, int>>& cases,
+                                       const py::bytes& pubkey, const py::bytes& sig) {
+        // the deferred record of each case as check_sig leaves it, one transaction entry per distinct raw
+        ConnectResult r;
+        r.all_forms = true;
+        std::map<std::string, u32> seen;
+        std::vector<Transaction> txs;
+        const Bytes pk = bytes_of(pubkey), sg = bytes_of(sig);
+        for (auto& c : cases) {
+            const std::string raw = std::get<0>(c);
+            auto it = seen.find(raw);
+            if (it == seen.end()) {
+                it = seen.emplace(raw, u32(txs.size())).first;
+                txs.push_back(tx_of(std::get<0>(c)));
+                r.forms.push_back(std::make_shared<const SighashTxForms>(txs.back()));
+            }
+            const Transaction& tx = txs[it->second];
+            const unsigned n_in = std::get<1>(c);
+            const Bytes code = bytes_of(std::get<2>(c));
+            const int ht = std::get<3>(c);
+            const SigVersion sv = std::get<5>(c) ? SigVersion::WITNESS_V0 : SigVersion::BASE;
+            PendingSig p{Uint256(), sg, pk};
+            if (sighash_deferrable(tx.vin.size(), tx.vout.size(), n_in, ht, sv)) {
+                p.device_hash = true;
+                p.tx_index = it->second;
+                p.n_in = n_in;
+                p.hash_type = ht;
+                p.code = sighash_emitted_code(code, sv);
+                p.sigversion = sv;
+                p.amount = std::get<4>(c);
+            } else {
+                p.msg = signature_hash(code, tx, n_in, ht, std::get<4>(c), sv);
+            }
+            r.sigs.push_back(std::move(p));
+            r.sig_at.emplace_back(it->second, n_in);
+        }
+        return r;
+    }, py::arg("cases"), py::arg("pubkey"), py::arg("sig"),
+       "a ConnectResult as connect_block(defer_all_forms=True) would leave it for these (raw tx, input, script code, "
+       "hash type, amount, sigversion) signatures, all with one key and signature: for packing them without a block");
     m.attr("SIGHASH_JOB_BYTES") = sizeof(SighashJob);
+    m.attr("SIGHASH_VAR_JOB_BYTES") = sizeof(SighashVarJob);
+    m.attr("SIGHASH_SEG_BYTES") = sizeof(SighashSeg);
+    m.attr("SIGHASH_VAR_MAX_SEGMENTS") = SIGHASH_VAR_MAX_SEGMENTS;
+    m.def("sighash_form", [](int sigversion, int hash_type) {
+        return std::string(sighash_form(sigversion ? SigVersion::WITNESS_V0 : SigVersion::BASE, hash_type));
+    }, "the form of a signature's message hash: all, none, single, each with |acp under ANYONECANPAY");
+    auto var_tables = [](const py::bytes& segs, const py::bytes& jobs, std::vector<SighashSeg>& sv,
+                         std::vector<SighashVarJob>& jv) {
+        const std::string s = segs, j = jobs;
+        if (s.size() % sizeof(SighashSeg)) throw std::invalid_argument("segment table is not a whole number of records");
+        if (j.size() % sizeof(SighashVarJob)) throw std::invalid_argument("job table is not a whole number of records");
+        sv.resize(s.size() / sizeof(SighashSeg));
+        jv.resize(j.size() / sizeof(SighashVarJob));
+        if (!s.empty()) std::memcpy(sv.data(), s.data(), s.size());
+        if (!j.empty()) std::memcpy(jv.data(), j.data(), j.size());
+    };
+    m.def("sighash_var_check", [var_tables](size_t arena_len, const py::bytes& segs, const py::bytes& jobs, py::object n_out) {
+        std::vector<SighashSeg> sv;
+        std::vector<SighashVarJob> jv;
+        var_tables(segs, jobs, sv, jv);
+        sighash_var_check(arena_len, sv.data(), sv.size(), jv.data(), jv.size(),
+                          n_out.is_none() ? jv.size() : n_out.cast<size_t>());
+    }, py::arg("arena_len"), py::arg("segs"), py::arg("jobs"), py::arg("n_out") = py::none(),
+       "ValueError on a segment outside the arena, a job whose segments pass the table or number more than "
+       "SIGHASH_VAR_MAX_SEGMENTS, a message of 2^29 bytes or more, or an output index >= n_out (default: the job count)");
+    m.def("sighash_var_model", [var_tables](const py::bytes& arena, const py::bytes& segs, const py::bytes& jobs) {
+        std::vector<SighashSeg> sv;
+        std::vector<SighashVarJob> jv;
+        var_tables(segs, jobs, sv, jv);
+        const Bytes a = bytes_of(arena);
+        Bytes out;
+        {
+            py::gil_scoped_release rel;
+            out = sighash_var_model(a, sv.data(), sv.size(), jv.data(), jv.size());
+        }
+        return pyb(out);
+    }, "host model of sighash_gather_var: SHA256d of each job's segments in order, 32 bytes per job");
     m.attr("SIGHASH_ARENA_SLACK") = SIGHASH_ARENA_SLACK;
     m.attr("SECP_KIND_INVALID") = SECP_KIND_INVALID;
     m.def("sighash_template", [](const py::bytes& tx_raw) {
@@ -429,9 +535,10 @@ void bind_script(py::module_& m) {
     m.def("connect_block", [](const Block& block, int height, CoinsView& view, bool check_scripts, bool defer_sigs,
                               py::object mtp_at, int64_t block_mtp, u32 flags, int threads, assets::State* asset_state,
                               const assets::Flags& asset_flags, const py::bytes& block_hash, bool sigcache,
-                              bool defer_sighash) {
+                              bool defer_sighash, bool defer_all_forms) {
         ConnectOptions opt;
         opt.defer_sighash = defer_sighash;
+        opt.defer_all_forms = defer_all_forms;
         opt.assets = asset_state;
         opt.asset_flags = asset_flags;
         const std::string bh = block_hash;
@@ -460,11 +567,13 @@ void bind_script(py::module_& m) {
        py::arg("defer_sigs") = false, py::arg("mtp_at") = py::none(), py::arg("block_mtp") = 0,
        py::arg("flags") = kBlockScriptFlags, py::arg("threads") = 1, py::arg("assets") = nullptr,
        py::arg("asset_flags") = assets::Flags{}, py::arg("block_hash") = py::bytes(), py::arg("sigcache") = true,
-       py::arg("defer_sighash") = false,
+       py::arg("defer_sighash") = false, py::arg("defer_all_forms") = false,
        "ConnectBlock against the view -> (ConnectResult, serialized CBlockUndo); the view is unchanged on failure. "
        "defer_sighash (with defer_sigs only): the legacy SIGHASH_ALL-form message hashes are left to the batch too "
        "(ConnectResult.sighash_pack); those signatures are not looked up in the signature cache, whose key is the "
-       "message, so their entries age out of the bounded cache instead of being erased on use");
+       "message, so their entries age out of the bounded cache instead of being erased on use. defer_all_forms (with "
+       "defer_sighash only): every form of both signature versions is left to the batch "
+       "(ConnectResult.sighash_pack_var), and the same holds for the witness signatures' cache entries");
     m.def("disconnect_block", [](const Block& block, const py::bytes& undo, CoinsView& view, assets::State* st,
                                  const py::bytes& asset_undo) {
         const Bytes au = bytes_of(asset_undo);

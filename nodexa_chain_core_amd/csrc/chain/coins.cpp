@@ -621,6 +621,7 @@ ConnectResult connect_block(const Block& block, int height, CoinsView& view, con
         res.sigs.clear();
         res.sig_at.clear();
         res.templates.clear();
+        res.forms.clear();
         return res;
     };
     struct Check {
@@ -634,7 +635,10 @@ ConnectResult connect_block(const Block& block, int height, CoinsView& view, con
     std::vector<Check> checks;
     std::vector<std::unique_ptr<PrecomputedTx>> caches(block.vtx.size());
     const bool defer_sighash = opt.defer_sigs && opt.defer_sighash;
-    if (defer_sighash) res.templates.resize(block.vtx.size());
+    const bool all_forms = defer_sighash && opt.defer_all_forms;
+    res.all_forms = all_forms;
+    if (all_forms) res.forms.resize(block.vtx.size());
+    else if (defer_sighash) res.templates.resize(block.vtx.size());
     for (size_t t = 0; t < block.vtx.size(); ++t) {
         const Transaction& tx = block.vtx[t];
         const Uint256 txid = tx.txid();
@@ -691,8 +695,9 @@ ConnectResult connect_block(const Block& block, int height, CoinsView& view, con
         res.sigop_cost += tx_sigop_cost(tx, spent, opt.script_flags);
         if (res.sigop_cost > kMaxBlockSigopsCost) return fail("bad-blk-sigops", 100);
         if (!tx.is_coinbase() && opt.check_scripts) {
-            caches[t] = std::make_unique<PrecomputedTx>(tx);
-            if (defer_sighash) res.templates[t] = std::make_shared<const SighashTemplate>(tx);
+            if (all_forms) res.forms[t] = std::make_shared<const SighashTxForms>(tx);  // holds the midstates too
+            else caches[t] = std::make_unique<PrecomputedTx>(tx);
+            if (defer_sighash && !all_forms) res.templates[t] = std::make_shared<const SighashTemplate>(tx);
             for (size_t i = 0; i < tx.vin.size(); ++i)
                 checks.push_back({u32(t), u32(i), spent[i]->out.value, spent[i]->out.script_pubkey});
         }
@@ -729,7 +734,8 @@ ConnectResult connect_block(const Block& block, int height, CoinsView& view, con
     // the script checks (CCheckQueue): inline, or spread over worker threads
     auto run = [&](Check& c) {
         const Transaction& tx = block.vtx[c.t];
-        TxSigChecker checker(&tx, c.i, c.value, caches[c.t].get());
+        TxSigChecker checker(&tx, c.i, c.value, all_forms ? &res.forms[c.t]->pre : caches[c.t].get());
+        checker.defer_all_forms = all_forms;
         if (opt.defer_sigs) checker.pending = &c.sigs;
         checker.defer_sighash = defer_sighash;
         checker.tx_index = c.t;

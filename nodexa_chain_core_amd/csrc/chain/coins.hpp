@@ -137,6 +137,10 @@ struct ConnectOptions {
     // signatures are not looked up in the signature cache, whose key is the message: their entries
     // age out of the bounded cache instead of being erased on use.
     bool defer_sighash = false;
+    // With defer_sighash: leave every form of both signature versions to the batch (NONE, SINGLE,
+    // ANYONECANPAY and witness v0 too; chain/sighash.hpp pack_sighash_var). None of the deferred
+    // signatures, witness ones included, is looked up in the signature cache.
+    bool defer_all_forms = false;
     bool sigcache = true;      // skip (and drop) signatures the mempool already verified (sigcache.hpp)
     bool sequence_locks = true;
     // median time past of the block at `height` of this block's chain (BIP68 time locks)
@@ -163,10 +167,15 @@ struct ConnectResult {
     Bytes asset_undo;                          // the asset journal of the block (with opt.assets)
     // with defer_sighash: the template of every transaction that has a deferred hash, by block index
     std::vector<std::shared_ptr<const SighashTemplate>> templates;
+    // with defer_all_forms instead: what the batch needs of every checked transaction, by block index
+    bool all_forms = false;
+    std::vector<std::shared_ptr<const SighashTxForms>> forms;
     // The message of sigs[k]: stored, or computed here on the host for a deferred hash.
     Uint256 sig_msg(size_t k) const {
         const PendingSig& p = sigs[k];
-        return p.device_hash ? sighash_from_template(*templates[p.tx_index], p.n_in, p.code, p.hash_type) : p.msg;
+        if (!p.device_hash) return p.msg;
+        if (all_forms) return sighash_from_forms(*forms[p.tx_index], p.n_in, p.code, p.hash_type, p.amount, p.sigversion);
+        return sighash_from_template(*templates[p.tx_index], p.n_in, p.code, p.hash_type);
     }
 };
 

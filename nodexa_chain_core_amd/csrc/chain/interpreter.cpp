@@ -185,6 +185,14 @@ Uint256 hash_bytes(const Bytes& b) {
     return h;
 }
 
+Uint256 hash_bytes(const u8* p, size_t n) {
+    Uint256 h;
+    sha256d(p, n, h.data);
+    return h;
+}
+
+size_t compact_size_len(u64 n) { return n < 253 ? 1 : n <= 0xffff ? 3 : n <= 0xffffffffu ? 5 : 9; }
+
 }  // namespace
 
 const char* script_error_name(ScriptError e) {
@@ -383,6 +391,100 @@ Uint256 sighash_from_template(const SighashTemplate& t, unsigned n_in, const Byt
     return hash_bytes(w.buf);
 }
 
+const char* sighash_form(SigVersion, int hash_type) {
+    const int base = hash_type & 0x1f;
+    const bool anyone = hash_type & SIGHASH_ANYONECANPAY;
+    if (base == SIGHASH_NONE) return anyone ? "none|acp" : "none";
+    if (base == SIGHASH_SINGLE) return anyone ? "single|acp" : "single";
+    return anyone ? "all|acp" : "all";
+}
+
+SighashTxForms::SighashTxForms(const Transaction& tx) : t(tx), pre(tx) {
+    // the template ends with: compact size of vout, the outputs, the lock time
+    size_t outs = 0;
+    for (auto& o : tx.vout) outs += 8 + compact_size_len(o.script_pubkey.size()) + o.script_pubkey.size();
+    size_t at = t.bytes.size() - 4 - outs;
+    outs_off = u32(at - compact_size_len(tx.vout.size()));
+    out_off.reserve(tx.vout.size() + 1);
+    for (auto& o : tx.vout) {
+        out_off.push_back(u32(at));
+        at += 8 + compact_size_len(o.script_pubkey.size()) + o.script_pubkey.size();
+    }
+    out_off.push_back(u32(at));
+}
+
+Bytes sighash_emitted_code(const Bytes& script_code, SigVersion sv) {
+    if (sv == SigVersion::BASE) return sighash_script_code(script_code);
+    Writer w;
+    w.var_bytes(script_code);
+    return std::move(w.buf);
+}
+
+Uint256 sighash_from_forms(const SighashTxForms& f, unsigned n_in, const Bytes& emitted_code, int32_t hash_type,
+                           Amount amount, SigVersion sv) {
+    const int base = hash_type & 0x1f;
+    const bool anyone = hash_type & SIGHASH_ANYONECANPAY;
+    const bool none = base == SIGHASH_NONE, single = base == SIGHASH_SINGLE;
+    const Bytes& T = f.t.bytes;
+    const size_t off = f.t.script_off.at(n_in);  // prevout at off - 36, sequence at off + 1
+    const u8* lock_time = T.data() + T.size() - 4;
+    Writer w;
+    if (sv == SigVersion::WITNESS_V0) {
+        static const u8 kZero[32] = {};
+        w.raw(T.data(), 4);
+        w.raw(anyone ? kZero : f.pre.prevouts.data, 32);
+        w.raw(anyone || none || single ? kZero : f.pre.sequence.data, 32);
+        w.raw(T.data() + off - 36, 36);
+        w.raw(emitted_code);
+        w.i64_(amount);
+        w.raw(T.data() + off + 1, 4);
+        if (!none && !single) {
+            w.raw(f.pre.outputs.data, 32);
+        } else if (single && n_in < f.n_out()) {
+            const Uint256 ho = hash_bytes(T.data() + f.out_off[n_in], f.out_off[n_in + 1] - f.out_off[n_in]);
+            w.raw(ho.data, 32);
+        } else {
+            w.raw(kZero, 32);
+        }
+        w.raw(lock_time, 4);
+        w.i32_(hash_type);
+        return hash_bytes(w.buf);
+    }
+    if (single && n_in >= f.n_out()) throw std::out_of_range("SIGHASH_SINGLE without a matching output is not deferred");
+    w.raw(T.data(), 4);
+    if (anyone) {
+        w.compact_size(1);
+        w.raw(T.data() + off - 36, 36);
+        w.raw(emitted_code);
+        w.raw(T.data() + off + 1, 4);
+    } else {
+        w.compact_size(f.n_in());
+        for (size_t i = 0; i < f.n_in(); ++i) {
+            const size_t o = f.t.script_off[i];
+            w.raw(T.data() + o - 36, 36);
+            if (i == n_in) w.raw(emitted_code);
+            else w.compact_size(0);
+            if (i != n_in && (none || single)) w.u32_(0);
+            else w.raw(T.data() + o + 1, 4);
+        }
+    }
+    if (none) {
+        w.compact_size(0);
+    } else if (single) {
+        w.compact_size(n_in + 1);
+        for (unsigned i = 0; i < n_in; ++i) {
+            w.i64_(-1);
+            w.compact_size(0);
+        }
+        w.raw(T.data() + f.out_off[n_in], f.out_off[n_in + 1] - f.out_off[n_in]);
+    } else {
+        w.raw(T.data() + f.outs_off, f.out_off.back() - f.outs_off);
+    }
+    w.raw(lock_time, 4);
+    w.i32_(hash_type);
+    return hash_bytes(w.buf);
+}
+
 Uint256 signature_hash(const Bytes& script_code, const Transaction& tx, unsigned n_in, int hash_type, Amount amount,
                        SigVersion sigversion, const PrecomputedTx* cache) {
     const int base = hash_type & 0x1f;
@@ -460,13 +562,26 @@ bool TxSigChecker::check_sig(const Bytes& sig_in, const Bytes& pubkey, const Byt
     if (sig_in.empty()) return false;
     const int hash_type = sig_in.back();
     const Bytes sig(sig_in.begin(), sig_in.end() - 1);
-    if (pending && defer_sighash && sighash_all_form(sv, hash_type) && n_in_ < tx_->vin.size()) {
+    if (pending && defer_sighash && !defer_all_forms && sighash_all_form(sv, hash_type) && n_in_ < tx_->vin.size()) {
         PendingSig p{Uint256(), sig, pubkey};
         p.device_hash = true;
         p.tx_index = tx_index;
         p.n_in = n_in_;
         p.hash_type = hash_type;
         p.code = sighash_script_code(script_code);
+        pending->push_back(std::move(p));
+        return true;
+    }
+    if (pending && defer_sighash && defer_all_forms &&
+        sighash_deferrable(tx_->vin.size(), tx_->vout.size(), n_in_, hash_type, sv)) {
+        PendingSig p{Uint256(), sig, pubkey};
+        p.device_hash = true;
+        p.tx_index = tx_index;
+        p.n_in = n_in_;
+        p.hash_type = hash_type;
+        p.code = sighash_emitted_code(script_code, sv);
+        p.sigversion = sv;
+        p.amount = amount_;
         pending->push_back(std::move(p));
         return true;
     }

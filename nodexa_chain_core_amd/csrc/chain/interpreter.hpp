@@ -120,6 +120,38 @@ inline bool sighash_all_form(SigVersion sv, int hash_type) {
 // SHA256d of the preimage above: equals signature_hash for every sighash_all_form signature.
 Uint256 sighash_from_template(const SighashTemplate& t, unsigned n_in, const Bytes& emitted_code, int32_t hash_type);
 
+// Every form of both signature versions, for the batch that hashes them all (defer_all_forms;
+// hip/kernels/sighash_var.hip). "all", "none", "single", each with "|acp" under ANYONECANPAY; the
+// odd base types count as "all", as the reference hashes them.
+const char* sighash_form(SigVersion sv, int hash_type);
+// What a batch needs of one transaction to lay out any of its signature hashes: the template, where
+// its outputs lie in it (out_off has vout.size() + 1 entries: each output's start, then the
+// lock time's; outs_off is the output count's compact size) and the BIP143 midstate hashes.
+struct SighashTxForms {
+    SighashTemplate t;
+    u32 outs_off = 0;
+    std::vector<u32> out_off;
+    PrecomputedTx pre;
+    SighashTxForms() = default;
+    explicit SighashTxForms(const Transaction& tx);
+    size_t n_in() const { return t.script_off.size(); }
+    size_t n_out() const { return out_off.size() - 1; }
+};
+// Whether defer_all_forms leaves this hash to the batch: everything but the legacy hashes whose
+// message is the constant one (input index past vin, or SINGLE without a matching output), which
+// have nothing to hash.
+inline bool sighash_deferrable(size_t n_vin, size_t n_vout, unsigned n_in, int hash_type, SigVersion sv) {
+    if (n_in >= n_vin) return false;
+    return sv == SigVersion::WITNESS_V0 || (hash_type & 0x1f) != SIGHASH_SINGLE || n_in < n_vout;
+}
+// The emitted script code of a deferred hash: sighash_script_code for a legacy signature, the
+// compact size and the code unchanged for witness v0.
+Bytes sighash_emitted_code(const Bytes& script_code, SigVersion sv);
+// signature_hash from the recorded pieces alone; legacy needs n_in < vin.size(), and SINGLE
+// n_in < vout.size() (the constant-one cases are never deferred).
+Uint256 sighash_from_forms(const SighashTxForms& f, unsigned n_in, const Bytes& emitted_code, int32_t hash_type,
+                           Amount amount, SigVersion sv);
+
 // Signature / locktime oracle used by EvalScript.
 class SigChecker {
 public:
@@ -145,6 +177,10 @@ struct PendingSig {
     u32 tx_index = 0, n_in = 0;
     int32_t hash_type = 0;
     Bytes code;
+    // With defer_all_forms every hash is left out (sighash_emitted_code in `code`), of both
+    // signature versions; witness v0 commits to the spent amount.
+    SigVersion sigversion = SigVersion::BASE;
+    Amount amount = 0;
 };
 
 class TxSigChecker : public SigChecker {
@@ -162,6 +198,9 @@ public:
     // With `pending`: leave the message hash of sighash_all_form signatures to the batch too.
     // Those signatures are not looked up in the signature cache (its key is the message).
     bool defer_sighash = false;
+    // With defer_sighash: leave the hash of every signature of both versions to the batch, except
+    // the legacy hashes whose message is the constant one (nothing to hash).
+    bool defer_all_forms = false;
     u32 tx_index = 0;  // the transaction's index in its block, recorded in deferred hashes
     // Signature cache (sigcache.hpp): STORE remembers every signature that verifies (mempool
     // acceptance); USE answers from the cache first and erases what it hits (block validation,

@@ -1,5 +1,6 @@
 #include "sighash.hpp"
 
+#include <algorithm>
 #include <cstring>
 #include <stdexcept>
 #include <string>
@@ -10,6 +11,8 @@
 namespace nodexa {
 
 SighashPack pack_sighash(const ConnectResult& res) {
+    // four fixed segments express the legacy ALL form only
+    if (res.all_forms) throw std::invalid_argument("pack_sighash: the block was connected with defer_all_forms");
     SighashPack out;
     out.secp_jobs.resize(res.sigs.size());
     std::vector<int64_t> tmpl_at(res.templates.size(), -1);  // arena offset of each template placed
@@ -76,6 +79,185 @@ Bytes sighash_gather_model(const Bytes& arena, const SighashJob* jobs, size_t n)
         msg.clear();
         for (int s = 0; s < SIGHASH_SEGMENTS; ++s)
             msg.insert(msg.end(), arena.begin() + jobs[k].off[s], arena.begin() + jobs[k].off[s] + jobs[k].len[s]);
+        sha256d(msg.data(), msg.size(), &out[k * 32]);
+    }
+    return out;
+}
+
+SighashVarPack pack_sighash_var(const ConnectResult& res) {
+    SighashVarPack out;
+    out.secp_jobs.resize(res.sigs.size());
+    Bytes& A = out.arena;
+    static const u8 kZero[32] = {};
+    // SINGLE's blanked outputs, once: as long as the furthest legacy SINGLE input needs
+    size_t blank_n = 0;
+    for (const PendingSig& p : res.sigs)
+        if (p.device_hash && p.sigversion == SigVersion::BASE && (p.hash_type & 0x1f) == SIGHASH_SINGLE)
+            blank_n = std::max<size_t>(blank_n, p.n_in);
+    for (size_t k = 0; k < blank_n; ++k) {
+        A.insert(A.end(), 8, 0xff);
+        A.push_back(0);
+    }
+    std::vector<int64_t> t_at(res.forms.size(), -1), z_at(res.forms.size(), -1);
+    auto put = [&](const u8* p, size_t n) { A.insert(A.end(), p, p + n); };
+    auto put_le32 = [&](u32 v) {
+        u8 b[4];
+        store_le32(b, v);
+        put(b, 4);
+    };
+    auto put_cs = [&](u64 n) {  // compact size (n < 2^32 here)
+        if (n < 253) {
+            A.push_back(u8(n));
+        } else if (n <= 0xffff) {
+            A.push_back(253);
+            A.push_back(u8(n));
+            A.push_back(u8(n >> 8));
+        } else {
+            A.push_back(254);
+            put_le32(u32(n));
+        }
+    };
+    for (size_t k = 0; k < res.sigs.size(); ++k) {
+        const PendingSig& p = res.sigs[k];
+        SecpVerifyJob& sj = out.secp_jobs[k];
+        if (!p.device_hash) {
+            secp::pack_verify_job(p.pubkey.data(), p.pubkey.size(), p.sig.data(), p.sig.size(), p.msg.data, sj);
+            ++out.host_jobs;
+            continue;
+        }
+        if (!res.all_forms)
+            throw std::invalid_argument("pack_sighash_var: the block was connected without defer_all_forms");
+        secp::pack_verify_job(p.pubkey.data(), p.pubkey.size(), p.sig.data(), p.sig.size(), kZero, sj);
+        const SighashTxForms& f = *res.forms.at(p.tx_index);
+        const Bytes& T = f.t.bytes;
+        const size_t off = f.t.script_off.at(p.n_in);
+        const int base = p.hash_type & 0x1f;
+        const bool anyone = p.hash_type & SIGHASH_ANYONECANPAY;
+        const bool none = base == SIGHASH_NONE, single = base == SIGHASH_SINGLE;
+        const u8* lock_time = T.data() + T.size() - 4;
+        SighashVarJob j{};
+        j.first_seg = u32(out.segs.size());
+        auto seg = [&](size_t at, size_t len) { out.segs.push_back(SighashSeg{u32(at), u32(len)}); };
+        if (p.sigversion == SigVersion::WITNESS_V0) {
+            const size_t at = A.size();
+            put(T.data(), 4);
+            put(anyone ? kZero : f.pre.prevouts.data, 32);
+            put(anyone || none || single ? kZero : f.pre.sequence.data, 32);
+            put(T.data() + off - 36, 36);
+            put(p.code.data(), p.code.size());
+            u8 amt[8];
+            store_le32(amt, u32(u64(p.amount)));
+            store_le32(amt + 4, u32(u64(p.amount) >> 32));
+            put(amt, 8);
+            put(T.data() + off + 1, 4);
+            if (!none && !single) {
+                put(f.pre.outputs.data, 32);
+            } else if (single && p.n_in < f.n_out()) {
+                u8 ho[32];
+                sha256d(T.data() + f.out_off[p.n_in], f.out_off[p.n_in + 1] - f.out_off[p.n_in], ho);
+                put(ho, 32);
+            } else {
+                put(kZero, 32);
+            }
+            put(lock_time, 4);
+            put_le32(u32(p.hash_type));
+            seg(at, A.size() - at);
+            ++out.device_v0;
+        } else {
+            if (single && p.n_in >= f.n_out()) throw std::logic_error("pack_sighash_var: a constant-one hash was deferred");
+            const bool need_t = !(none && !anyone);  // NONE reads only Z
+            if (need_t && t_at[p.tx_index] < 0) {
+                t_at[p.tx_index] = int64_t(A.size());
+                put(T.data(), T.size());
+            }
+            if ((none || single) && !anyone && z_at[p.tx_index] < 0) {
+                z_at[p.tx_index] = int64_t(A.size());
+                put(T.data(), f.outs_off);
+                for (u32 o : f.t.script_off) std::memset(A.data() + z_at[p.tx_index] + o + 1, 0, 4);
+            }
+            const size_t tb = need_t ? size_t(t_at[p.tx_index]) : 0, zb = size_t(std::max<int64_t>(z_at[p.tx_index], 0));
+            if (anyone) {
+                const size_t head = A.size();
+                put(T.data(), 4);
+                A.push_back(1);
+                seg(head, 5);
+                seg(tb + off - 36, 36);
+            } else if (none || single) {
+                seg(zb, off);
+            } else {
+                seg(tb, off);
+            }
+            // the emitted code, and what follows it up to the next shared range
+            size_t at = A.size();
+            put(p.code.data(), p.code.size());
+            if (anyone || none || single) put(T.data() + off + 1, 4);
+            if ((none || single) && !anyone) {
+                seg(at, A.size() - at);
+                seg(zb + off + 5, f.outs_off - off - 5);
+                at = A.size();
+            }
+            if (none) {
+                A.push_back(0);
+                put(lock_time, 4);
+                put_le32(u32(p.hash_type));
+                seg(at, A.size() - at);
+            } else if (single) {
+                put_cs(u64(p.n_in) + 1);
+                seg(at, A.size() - at);
+                seg(0, 9 * size_t(p.n_in));
+                seg(tb + f.out_off[p.n_in], f.out_off[p.n_in + 1] - f.out_off[p.n_in]);
+                at = A.size();
+                put(lock_time, 4);
+                put_le32(u32(p.hash_type));
+                seg(at, 8);
+            } else {
+                seg(at, A.size() - at);
+                if (anyone) seg(tb + f.outs_off, T.size() - f.outs_off);
+                else seg(tb + off + 1, T.size() - off - 1);
+                at = A.size();
+                put_le32(u32(p.hash_type));
+                seg(at, 4);
+            }
+            if (!sighash_all_form(SigVersion::BASE, p.hash_type)) ++out.device_partial;
+        }
+        if (A.size() > 0xffffffffULL) throw std::length_error("sighash arena exceeds 4 GiB");
+        j.n_seg = u32(out.segs.size()) - j.first_seg;
+        j.out_index = u32(k);
+        j.kind = sj.kind;  // INVALID stays INVALID: host parsing already failed
+        sj.kind = SECP_KIND_INVALID;
+        out.jobs.push_back(j);
+        ++out.device_jobs;
+    }
+    return out;
+}
+
+void sighash_var_check(size_t arena_len, const SighashSeg* segs, size_t n_segs, const SighashVarJob* jobs, size_t n,
+                       size_t n_out) {
+    for (size_t s = 0; s < n_segs; ++s)
+        if (u64(segs[s].off) + segs[s].len > arena_len)
+            throw std::invalid_argument("sighash segment " + std::to_string(s) + " lies outside the arena");
+    for (size_t k = 0; k < n; ++k) {
+        const std::string who = "sighash job " + std::to_string(k);
+        if (jobs[k].n_seg > SIGHASH_VAR_MAX_SEGMENTS) throw std::invalid_argument(who + ": too many segments");
+        if (u64(jobs[k].first_seg) + jobs[k].n_seg > n_segs)
+            throw std::invalid_argument(who + ": segments past the end of the table");
+        u64 total = 0;
+        for (u32 s = 0; s < jobs[k].n_seg; ++s) total += segs[jobs[k].first_seg + s].len;
+        if (total >= (1u << 29)) throw std::invalid_argument(who + ": message too long");
+        if (jobs[k].out_index >= n_out) throw std::invalid_argument(who + ": output index out of range");
+    }
+}
+
+Bytes sighash_var_model(const Bytes& arena, const SighashSeg* segs, size_t n_segs, const SighashVarJob* jobs, size_t n) {
+    sighash_var_check(arena.size(), segs, n_segs, jobs, n, size_t(-1));
+    Bytes out(n * 32);
+    Bytes msg;
+    for (size_t k = 0; k < n; ++k) {
+        msg.clear();
+        for (u32 s = 0; s < jobs[k].n_seg; ++s) {
+            const SighashSeg& g = segs[jobs[k].first_seg + s];
+            msg.insert(msg.end(), arena.begin() + g.off, arena.begin() + g.off + g.len);
+        }
         sha256d(msg.data(), msg.size(), &out[k * 32]);
     }
     return out;

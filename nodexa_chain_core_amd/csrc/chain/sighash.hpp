@@ -33,4 +33,43 @@ void sighash_check_jobs(size_t arena_len, const SighashJob* jobs, size_t n, size
 // 32 raw bytes each, in job order.
 Bytes sighash_gather_model(const Bytes& arena, const SighashJob* jobs, size_t n);
 
+// ---- every form of both signature versions (hip/kernels/sighash_var.hip)
+//
+// connect_block with defer_all_forms leaves out every message hash but the legacy constant one.
+// pack_sighash_var lays them out over one arena and a segment table, at most
+// SIGHASH_VAR_MAX_SEGMENTS ranges per signature. Placed once per transaction, and only when one of
+// its signatures needs it: the template T, and Z, the head of T up to the outputs with every
+// sequence zeroed (NONE / SINGLE). Placed once per arena: SINGLE's run of blanked outputs
+// (ff x 8, 00), of which input i uses the first 9 i bytes. Per signature (| joins the segments;
+// e = emitted code, seq = the input's sequence, lt = lock time, ht = hash type, all little-endian):
+//   all         T[:off] | e | T[off+1:] | ht
+//   none        Z[:off] | e seq | Z[off+5:] | 00 lt ht
+//   single      Z[:off] | e seq | Z[off+5:] | cs(i+1) | blank[:9i] | T[output i] | lt ht
+//   all|acp     version 01 | T[prevout i] | e seq | T[outputs, lt] | ht
+//   none|acp    version 01 | T[prevout i] | e seq 00 lt ht
+//   single|acp  version 01 | T[prevout i] | e seq cs(i+1) | blank[:9i] | T[output i] | lt ht
+//   witness v0  the whole BIP143 preimage (e + 156 bytes; the three midstate hashes are the
+//               transaction's PrecomputedTx, SINGLE's output hash is computed here) as one segment
+// so a legacy signature adds at most len(e) + 22 bytes to the arena and the arena stays linear in
+// the block size.
+struct SighashVarPack {
+    Bytes arena;
+    std::vector<SighashSeg> segs;
+    std::vector<SighashVarJob> jobs;       // block order
+    std::vector<SecpVerifyJob> secp_jobs;  // as SighashPack's: device-hashed records INVALID with z = 0
+    size_t device_jobs = 0, host_jobs = 0;
+    size_t device_v0 = 0, device_partial = 0;  // of device_jobs: witness v0, legacy other than the ALL form
+};
+SighashVarPack pack_sighash_var(const ConnectResult& res);
+
+// Throws std::invalid_argument on a segment outside [0, arena_len) (32-bit wrap included), a job
+// whose first_seg + n_seg passes the table, n_seg > SIGHASH_VAR_MAX_SEGMENTS, a message of 2^29
+// bytes or more, or an out_index >= n_out.
+void sighash_var_check(size_t arena_len, const SighashSeg* segs, size_t n_segs, const SighashVarJob* jobs, size_t n,
+                       size_t n_out);
+
+// The definition of sighash_gather_var: digest k = SHA256d of job k's segments in order, 32 raw
+// bytes each, in job order.
+Bytes sighash_var_model(const Bytes& arena, const SighashSeg* segs, size_t n_segs, const SighashVarJob* jobs, size_t n);
+
 }  // namespace nodexa

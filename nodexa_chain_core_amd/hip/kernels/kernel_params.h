@@ -167,6 +167,28 @@ struct SighashParams {
     uint32_t pad;
 };
 
+// Gathered SHA-256d for signature hashes of every form (sighash_var.hip sighash_gather_var): the
+// message of job k is the concatenation of segs[first_seg .. first_seg + n_seg), each a byte range
+// of the arena that may be empty; n_seg may be 0 (the empty message). Output as SighashJob's.
+#define SIGHASH_VAR_MAX_SEGMENTS 8
+struct SighashSeg {
+    uint32_t off, len;               // arena byte range
+};
+struct SighashVarJob {
+    uint32_t first_seg, n_seg;       // the job's entries of the segment table
+    uint32_t out_index;              // row of `digests` / entry of `secp_jobs` this job fills
+    uint32_t kind;                   // the signature's real SECP_KIND_*, written together with z
+};
+struct SighashVarParams {
+    const uint8_t* arena;
+    const struct SighashSeg* segs;
+    const struct SighashVarJob* jobs;
+    uint8_t* digests;                // nullable: out_index x 32 raw digest bytes
+    struct SecpVerifyJob* secp_jobs; // nullable: z and kind of entry out_index are written
+    uint32_t n;
+    uint32_t n_segs;
+};
+
 // Batch verification of packed Equihash(200,9) solutions (equihash.hip eq_verify).
 #define EQ_SOL_WORDS 336  // 1344 bytes = 512 x 21-bit big-endian indices
 struct EquihashVerifyParams {

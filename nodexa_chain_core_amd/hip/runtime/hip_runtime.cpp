@@ -638,6 +638,28 @@ PYBIND11_MODULE(_hip, m) {
         k.launch_bytes(dim3((n + 255) / 256), dim3(256), 0, as_stream(stream), &p, sizeof(p));
     });
 
+    // ---- the same for every form of signature hash (sighash_var.hip): n SighashVarJob records, each
+    // naming a run of the n_segs-entry SighashSeg table. The caller has validated both tables
+    // (_core.sighash_var_check) and keeps SIGHASH_ARENA_SLACK readable bytes after the arena.
+    m.attr("SIGHASH_VAR_JOB_BYTES") = sizeof(SighashVarJob);
+    m.attr("SIGHASH_SEG_BYTES") = sizeof(SighashSeg);
+    m.def("launch_sighash_gather_var", [](const Kernel& k, uintptr_t arena, uintptr_t segs, uint32_t n_segs,
+                                          uintptr_t jobs, uint32_t n, uintptr_t digests, uintptr_t secp_jobs,
+                                          uintptr_t stream) {
+        if (n == 0) return;
+        if (!arena || !segs || !jobs) throw std::invalid_argument("sighash: null arena, segment or job table");
+        if (!digests && !secp_jobs) throw std::invalid_argument("sighash: no output requested");
+        SighashVarParams p{};
+        p.arena = reinterpret_cast<const uint8_t*>(arena);
+        p.segs = reinterpret_cast<const SighashSeg*>(segs);
+        p.jobs = reinterpret_cast<const SighashVarJob*>(jobs);
+        p.digests = reinterpret_cast<uint8_t*>(digests);
+        p.secp_jobs = reinterpret_cast<SecpVerifyJob*>(secp_jobs);
+        p.n = n;
+        p.n_segs = n_segs;
+        k.launch_bytes(dim3((n + 255) / 256), dim3(256), 0, as_stream(stream), &p, sizeof(p));
+    });
+
     // ---- Equihash(200,9): one full Wagner solve for `num_inst` inputs, enqueued on `stream`
     m.attr("EQ_BUCKETS") = EQ_BUCKETS;
     m.attr("EQ_WORDS") = EQ_WORDS;

@@ -319,9 +319,11 @@ class Node:
         cores = os.cpu_count() or 1
         self.state.script_threads = max(1, min(16, cores + par if par <= 0 else par))
         self.state.gpu_signatures = a.get("gpusigs", "auto")  # -gpusigs=auto|on|off: GPU batch ECDSA in blocks
-        # -gpusighash=0|1: with the GPU batch, also compute the legacy SIGHASH_ALL-form message hashes on
-        # the GPU (ops/sighash); without a GPU batch it has nothing to act on
+        # -gpusighash=0|1|2: with the GPU batch, also compute message hashes on the GPU (ops/sighash):
+        # 1 = the legacy SIGHASH_ALL form, 2 = every form of legacy and witness-v0 signatures; without a
+        # GPU batch it has nothing to act on
         self.state.gpu_sighash = a.get_bool("gpusighash", False)
+        self.state.gpu_sighash_forms = "all" if (a.get("gpusighash") or "").strip() == "2" else "legacy-all"
         if self.datadir is not None:  # fee_estimates.dat (src/init.cpp: est_filein), before the mempool
             self.state.load_fee_estimates(os.path.join(self.datadir, "fee_estimates.dat"))
         if self.datadir is not None and a.get_bool("persistmempool", True):  # -persistmempool (LoadMempool)

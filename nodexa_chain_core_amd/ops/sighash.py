@@ -12,6 +12,12 @@ the records are uploaded INVALID, so a signature the kernel never reached can on
 
 `digests` is the kernel on its own; `verify_block_sigs` is the block path: gather, then
 `secp_verify_batch` on the same stream, verdicts only coming back.
+
+A block connected with `defer_all_forms=True` leaves every form of both signature versions out
+(NONE, SINGLE, ANYONECANPAY, witness v0). `ConnectResult.sighash_pack_var()` names each message
+through a table of up to SIGHASH_VAR_MAX_SEGMENTS arena ranges and `sighash_gather_var`
+(hip/kernels/sighash_var.hip) hashes them; `digests_var` and `gather_var_into_secp` are that
+kernel on its own, and `verify_block_sigs` takes this path for such a result.
 """
 from __future__ import annotations
 
@@ -23,6 +29,8 @@ from ..utils.trace import traced
 from . import runtime, secp
 
 JOB_BYTES = _core.SIGHASH_JOB_BYTES
+VAR_JOB_BYTES = _core.SIGHASH_VAR_JOB_BYTES
+SEG_BYTES = _core.SIGHASH_SEG_BYTES
 
 
 def _upload_arena(arena: bytes, dev: torch.device) -> torch.Tensor:
@@ -79,10 +87,59 @@ def gather_into_secp(arena: bytes, jobs: bytes, secp_jobs: bytes, device: int | 
         return d_secp.cpu().numpy().tobytes()
 
 
+def _upload_var(arena: bytes, segs: bytes, jobs: bytes, n_out: int, dev: torch.device):
+    # nothing malformed reaches the device: every segment inside the arena, every job inside the
+    # segment table, every output in range
+    _core.sighash_var_check(len(arena), segs, jobs, n_out)
+    # a job table may name no segment at all: the kernel still gets a valid (unread) table
+    d_segs = torch.frombuffer(bytearray(segs or bytes(SEG_BYTES)), dtype=torch.int32).to(dev)
+    return _upload_arena(arena, dev), d_segs, torch.frombuffer(bytearray(jobs), dtype=torch.int32).to(dev)
+
+
+def digests_var(arena: bytes, segs: bytes, jobs: bytes, device: int | None = None) -> np.ndarray:
+    """(n, 32) uint8: SHA256d of each job's segments in order, row = the job's output index (which
+    must be below the job count). Equals `_core.sighash_var_model` row for row when the output
+    indices are 0..n-1."""
+    n = len(jobs) // VAR_JOB_BYTES
+    if n == 0:
+        _core.sighash_var_check(len(arena), segs, jobs, 0)
+        return np.zeros((0, 32), np.uint8)
+    runtime.require_gpu()
+    dev = _device(device)
+    with torch.cuda.device(dev):
+        d_arena, d_segs, d_jobs = _upload_var(arena, segs, jobs, n, dev)
+        out = torch.zeros((n, 32), dtype=torch.uint8, device=dev)
+        runtime.hip().launch_sighash_gather_var(runtime.static_kernel("sighash_var", "sighash_gather_var"),
+                                                d_arena.data_ptr(), d_segs.data_ptr(), len(segs) // SEG_BYTES,
+                                                d_jobs.data_ptr(), n, out.data_ptr(), 0,
+                                                runtime.current_stream_handle())
+        return out.cpu().numpy()
+
+
+def gather_var_into_secp(arena: bytes, segs: bytes, jobs: bytes, secp_jobs: bytes, device: int | None = None) -> bytes:
+    """`gather_into_secp` for a segment-table job set: the SecpVerifyJob array as the device holds
+    it after sighash_gather_var."""
+    n = len(jobs) // VAR_JOB_BYTES
+    n_secp = len(secp_jobs) // _core.SECP_JOB_BYTES
+    if n == 0:
+        return bytes(secp_jobs)
+    runtime.require_gpu()
+    dev = _device(device)
+    with torch.cuda.device(dev):
+        d_arena, d_segs, d_jobs = _upload_var(arena, segs, jobs, n_secp, dev)
+        d_secp = torch.frombuffer(bytearray(secp_jobs), dtype=torch.int32).to(dev)
+        runtime.hip().launch_sighash_gather_var(runtime.static_kernel("sighash_var", "sighash_gather_var"),
+                                                d_arena.data_ptr(), d_segs.data_ptr(), len(segs) // SEG_BYTES,
+                                                d_jobs.data_ptr(), n, 0, d_secp.data_ptr(),
+                                                runtime.current_stream_handle())
+        return d_secp.cpu().numpy().tobytes()
+
+
 @traced("sighash.verify_block_sigs")
 def verify_block_sigs(res, device: int | None = None) -> list[bool]:
     """CPubKey::Verify's answer for every deferred signature of a `connect_block(defer_sigs=True,
-    defer_sighash=True)` result, in the order of `res.sig_items()`. The message hashes left to the
+    defer_sighash=True)` result (with or without `defer_all_forms`), in the order of
+    `res.sig_items()`. The message hashes left to the
     batch are computed on the device and never come back; only the verdicts do. A verdict 2
     (degenerate addition) is re-checked on the host with the host-computed message."""
     n = res.num_sigs
@@ -91,13 +148,22 @@ def verify_block_sigs(res, device: int | None = None) -> list[bool]:
     runtime.require_gpu()
     h = runtime.hip()
     dev = _device(device)
-    arena, jobs, secp_jobs, n_dev, _n_host = res.sighash_pack()
+    var = res.all_forms
+    if var:
+        arena, segs, jobs, secp_jobs, n_dev, _n_host = res.sighash_pack_var()
+    else:
+        arena, jobs, secp_jobs, n_dev, _n_host = res.sighash_pack()
     with torch.cuda.device(dev):
         stream = runtime.current_stream_handle()
         d_secp = torch.frombuffer(bytearray(secp_jobs), dtype=torch.int32).to(dev)
         out = torch.empty(n, dtype=torch.int32, device=dev)
         gtab = secp._gen_table(dev)  # uploaded on first use: before the launches, not between them
-        if n_dev:
+        if n_dev and var:
+            d_arena, d_segs, d_jobs = _upload_var(arena, segs, jobs, n, dev)
+            h.launch_sighash_gather_var(runtime.static_kernel("sighash_var", "sighash_gather_var"), d_arena.data_ptr(),
+                                        d_segs.data_ptr(), len(segs) // SEG_BYTES, d_jobs.data_ptr(), n_dev, 0,
+                                        d_secp.data_ptr(), stream)
+        elif n_dev:
             d_arena, d_jobs = _upload_jobs(arena, jobs, n, dev)
             h.launch_sighash_gather(runtime.static_kernel("sighash", "sighash_gather_batch"), d_arena.data_ptr(),
                                     d_jobs.data_ptr(), n_dev, 0, d_secp.data_ptr(), stream)
