@@ -71,6 +71,19 @@ void bind_extra(py::module_& m) {
         d["target_timespan"] = u32(kDgwPastBlocks * c.pow_target_spacing);
         return d;
     });
+    // The host model of that kernel (chain/pow_rules.cpp dgw_average) over a raw series of
+    // little-endian u32 (nTime, nBits) pairs: the nBits of the header after series entry j, whose
+    // nTime is next_time. Test hook (tests/test_dgw_series.py, tests/test_gpu_dgw_edges.py).
+    m.def("dgw_average", [](const ChainParams& p, const py::bytes& times, const py::bytes& bits, int64_t j,
+                            u32 next_time) {
+        const std::string t = times, b = bits;
+        if (t.size() != b.size() || t.size() % 4) throw std::invalid_argument("series: the same number of u32 values");
+        if (j >= int64_t(t.size() / 4)) throw std::out_of_range("dgw_average: j past the series");
+        std::vector<u32> tv(t.size() / 4), bv(tv.size());
+        std::memcpy(tv.data(), t.data(), t.size());
+        std::memcpy(bv.data(), b.data(), b.size());
+        return dgw_average(tv.data(), bv.data(), j, next_time, p);
+    }, py::arg("params"), py::arg("times"), py::arg("bits"), py::arg("j"), py::arg("next_time"));
 
     // ------------------------------------------------ batch header verification (models/verify.py)
     // One pass over a header batch: for every KawPow header the 48-byte job record the GPU

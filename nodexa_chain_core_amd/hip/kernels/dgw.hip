@@ -2,8 +2,11 @@
 // batch computes the nBits that header must carry, from the 180 (nTime, nBits) pairs before it.
 //
 // Reference: DarkGravityWave (src/pow.cpp:18-102), serial per header under cs_main. The host
-// model is csrc/chain/pow_rules.cpp dgw_average; this kernel is its bit-exact twin, checked
-// against it over a 10k-header fixture in tests/test_gpu_verify.py:
+// model is csrc/chain/pow_rules.cpp dgw_average; this kernel is its bit-exact twin. Both are
+// checked against an independent big-int DarkGravityWave (tests/dgw_oracle.py) on adversarial raw
+// series: this kernel in tests/test_gpu_dgw_edges.py (arithmetic edges, the index logic below, era
+// switches, the 0 sentinel), the host model in tests/test_dgw_series.py; tests/test_gpu_verify.py
+// compares the twins over a 10k-header fixture:
 //   * the running "average" avg = (avg * count + target) / (count + 1) over the 180 blocks,
 //     newest first, on 32-bit limbs with the reference's mod-2^256 wrap-around, the division by
 //     count + 1 <= 181 exact through a 64-bit reciprocal (every partial dividend is < d * 2^32);

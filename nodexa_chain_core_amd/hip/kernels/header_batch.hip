@@ -14,6 +14,11 @@
 // hb_jobs writes the KawPow block hashes, so hashes + nBits are complete once the side stream and
 // hb_jobs are done: an early copy of them lets the host prepare the index insert while the full
 // hashes run, and one final device-to-host copy brings back codes, hashes and nBits together.
+//
+// Checked in tests/test_gpu_header_verdicts.py: hb_verdict and hb_eq_scatter alone on constructed
+// buffers (final == boundary, boundary == powLimit, one-word mix differences, the checkpoint rule,
+// exotic nBits) against CheckProofOfWork on Python integers; the whole pipeline over the fixtures in
+// tests/test_gpu_resident_verify.py.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -85,13 +90,17 @@ extern "C" __global__ __launch_bounds__(256) void hb_verdict(HeaderBatchParams p
         const uint8_t b = mo[64 + k];
         cmp = a < b ? -1 : (a > b ? 1 : 0);
     }
-    // CheckProofOfWork also refuses a target above powLimit (the boundary is big-endian here)
+    // CheckProofOfWork also refuses a target above powLimit (the boundary is big-endian here) and a
+    // zero target, which is what the mix-only pass writes for a negative or overflowing nBits: a
+    // zero final must not pass against it
     int lim = 0;
-    for (int k = 0; k < 32 && lim == 0; ++k) {
+    uint8_t any = 0;
+    for (int k = 0; k < 32; ++k) {
         const uint8_t a = mo[64 + k], b = p.pow_limit[31 - k];
-        lim = a < b ? -1 : (a > b ? 1 : 0);
+        any |= a;
+        if (lim == 0) lim = a < b ? -1 : (a > b ? 1 : 0);
     }
-    uint8_t code = (cmp <= 0 && lim <= 0) ? 0 : 2;
+    uint8_t code = (cmp <= 0 && lim <= 0 && any != 0) ? 0 : 2;
     if (code == 0 && !below_cp) {
         bool same = true;
 #pragma unroll

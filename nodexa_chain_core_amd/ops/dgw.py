@@ -4,8 +4,10 @@
 (`HeaderChain.dgw_series`: up to 180 ancestors then the batch) into the nBits every header must
 carry, one GPU thread per header. The result goes to `HeaderChain.accept_headers(bits=...)`, so
 the host's contextual stage keeps only the serial index updates. Bit-exact with the host's
-dgw_average (csrc/chain/pow_rules.cpp), the reference's DarkGravityWave (src/pow.cpp:18-102);
-tests/test_gpu_verify.py compares the two over the 10k-header fixture."""
+dgw_average (csrc/chain/pow_rules.cpp), the reference's DarkGravityWave (src/pow.cpp:18-102):
+tests/test_gpu_dgw_edges.py checks the kernel against an independent big-int model
+(tests/dgw_oracle.py) on adversarial raw series, tests/test_dgw_series.py does the same for the
+host model, and tests/test_gpu_verify.py compares the two over the 10k-header fixture."""
 from __future__ import annotations
 
 import numpy as np
