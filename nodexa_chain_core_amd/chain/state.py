@@ -15,7 +15,9 @@ Signatures in blocks are verified in one GPU batch per block when a GPU is prese
 (ops/secp.verify_batch; the reference spreads them over its CCheckQueue CPU threads). The batch
 result is only trusted where it cannot differ from the reference: any input whose signature the
 batch rejects is re-run on the host, and a block whose deferred run fails is re-connected with
-host checks (`_connect_one`).
+host checks (`_connect_one`). With -gpusigwindow the batch covers a run of consecutive blocks
+instead: they are connected speculatively and made final, in order, once the run has verified
+(`_connect_windowed`).
 
 Storage (-dbformat, `detect_db_format`): by default the block index and the UTXO set live in
 LevelDB-format stores with the reference's keys — blocks/index/ (BlockTreeDB: 'b' CDiskBlockIndex
@@ -83,6 +85,13 @@ class ValidationInterface:
     def connect_tip(self, block, index, undo: bytes) -> None: ...
 
     def disconnect_tip(self, block, index, undo: bytes) -> None: ...
+
+    # With -gpusigwindow, connect_tip for a block fires once its window has verified, when the UTXO
+    # set and the asset state may already hold the window's later blocks. A listener that reads
+    # either of them in connect_tip answers True here for such a block: the window then ends with
+    # it, and the listener finds the state at exactly that block, as without the flag.
+    def needs_exact_state(self, block, index) -> bool:
+        return False
 
     def new_asset_message(self, message) -> None: ...
 
@@ -172,6 +181,7 @@ ROLLING_FEE_HALFLIFE = 60 * 60 * 12                                   # src/txme
 MEMPOOL_ENTRY_OVERHEAD = 320  # bytes of bookkeeping per entry counted by mempool_usage (DynamicMemoryUsage analogue)
 MAX_STANDARD_SCRIPTSIG_SIZE = 1650
 GPU_SIG_BATCH_MIN = 16                 # below this many signatures a block is checked on the host
+SIG_WINDOW_MAX_BLOCK_BYTES = 64 << 20  # -gpusigwindow: a window closes once it holds this much block data
 
 
 def _compact_size(n: int) -> bytes:
@@ -264,8 +274,19 @@ class ChainState:
         self.gpu_sighash_forms = "legacy-all"  # "all" with -gpusighash=2: every form, witness v0 included
         # gpu_sighashes_v0 / gpu_sighashes_partial: of gpu_sighashes, the witness-v0 hashes and the
         # legacy hashes of another form than ALL's (both only with -gpusighash=2)
+        # gpu_windows / window_blocks / window_sigs: device passes over a window of blocks
+        # (-gpusigwindow), the blocks and signatures they covered; window_rollbacks: windows that
+        # were rolled back to a block whose signatures failed
         self.sig_stats = {"gpu_batches": 0, "gpu_sigs": 0, "host_rechecks": 0, "gpu_sighashes": 0,
-                          "host_sighashes": 0, "gpu_sighashes_v0": 0, "gpu_sighashes_partial": 0}
+                          "host_sighashes": 0, "gpu_sighashes_v0": 0, "gpu_sighashes_partial": 0,
+                          "gpu_windows": 0, "window_blocks": 0, "window_sigs": 0, "window_rollbacks": 0}
+        # -gpusigwindow=<signatures>: with the GPU batch, _activate connects consecutive blocks
+        # speculatively and verifies their signatures in one device pass of about this many (0: off,
+        # every block on its own)
+        self.gpu_sig_window = 0
+        # what verifies a window: list of ConnectResults -> one list of verdicts per result. None:
+        # ops.sighash.verify_window, on a GPU; anything else is called without asking for one
+        self.sig_window_verifier = None
         self.db_format = detect_db_format(datadir, db_format)
         self.coins_db = None
         self._coins_obf = b""
@@ -1163,6 +1184,15 @@ class ChainState:
                 path.append(x)
                 x = self.chain.find(x.prev_hash)
             restart = False
+            if self._sig_window_on():
+                bad = self._connect_windowed(list(reversed(path)), connected)
+                if bad is not None:
+                    failed[bad[0].hash] = bad[1]
+                    self.chain.invalidate(bad[0].hash)
+                    restart = True
+                if not restart:
+                    break
+                continue
             for idx in reversed(path):
                 blk = self.get_block(idx.hash)
                 if blk is None:
@@ -1193,6 +1223,10 @@ class ChainState:
         n_inputs = sum(len(tx.vin) for tx in block.vtx[1:])
         if n_inputs < (1 if self.gpu_signatures == "on" else GPU_SIG_BATCH_MIN):
             return False
+        return self._gpu_present()
+
+    @staticmethod
+    def _gpu_present() -> bool:
         try:
             import torch
 
@@ -1200,9 +1234,29 @@ class ChainState:
         except ImportError:  # pragma: no cover
             return False
 
+    def _sig_window_on(self) -> bool:
+        """-gpusigwindow acts only where the GPU signature batch does (-gpusigs auto / on with a
+        GPU); a verifier set by hand is taken without asking for one."""
+        if self.gpu_sig_window <= 0 or self.gpu_signatures == "off":
+            return False
+        return self.sig_window_verifier is not None or self._gpu_present()
+
     def _connect_one(self, block, idx) -> ValidationState:
         """ConnectTip: connect `block` at `idx`, then the coinbase / community-fund rules on the
         block's real fees; on any failure the UTXO set is left as it was."""
+        st, res, undo = self._connect_speculative(block, idx, False)
+        if not st.ok:
+            return st
+        self._connect_final(block, idx, res, undo)
+        self._flush_if_due()
+        return st
+
+    def _connect_speculative(self, block, idx, windowed: bool):
+        """The half of ConnectTip that only touches the in-memory UTXO set and asset state:
+        connect_block and the coinbase / community-fund rules on the block's real fees. ->
+        (state, ConnectResult, undo); on failure the UTXO set is left as it was. `windowed`: the
+        deferred signatures are left in the result for the window's device pass
+        (_verify_window) instead of being verified here."""
         height = idx.height
         prev = self.chain.find(idx.prev_hash)
         mtp_prev = prev.median_time_past()
@@ -1214,7 +1268,7 @@ class ChainState:
         check_scripts = not self._assumed_valid(idx)
         if not check_scripts:
             self.scripts_skipped += 1
-        gpu = check_scripts and self._use_gpu_for(block)
+        gpu = check_scripts and (windowed or self._use_gpu_for(block))
         par = self.script_threads
         aflags = self.asset_flags(prev)
 
@@ -1234,9 +1288,9 @@ class ChainState:
             # failing: the host run decides
             res, undo = connect(False)
         if not res.ok:
-            return ValidationState.invalid(res.reject, res.dos)
+            return ValidationState.invalid(res.reject, res.dos), res, undo
         aundo = res.asset_undo
-        if gpu and res.num_sigs:
+        if gpu and res.num_sigs and not windowed:
             from ..ops import secp
 
             if gpu_hash:
@@ -1258,11 +1312,19 @@ class ChainState:
                 ok, err = _core.verify_input_host(block, t, i, value, spk, flags)
                 if not ok:
                     _core.disconnect_block(block, undo, self.coins, self.assets, aundo)
-                    return ValidationState.invalid(f"mandatory-script-verify-flag-failed ({err})", 100)
+                    return ValidationState.invalid(f"mandatory-script-verify-flag-failed ({err})", 100), res, undo
         ok, reason, dos = _core.check_coinbase_rewards(block, self.params, height, res.fees, True)
         if not ok:
             _core.disconnect_block(block, undo, self.coins, self.assets, aundo)
-            return ValidationState.invalid(reason, dos)
+            return ValidationState.invalid(reason, dos), res, undo
+        return ValidationState(), res, undo
+
+    def _connect_final(self, block, idx, res, undo) -> None:
+        """The half of ConnectTip that others see: the undo and index records, the UTXO set's best
+        block, the fee estimator and the connect_tip event. The flush check is the caller's
+        (_flush_if_due), once nothing speculative is left in the UTXO set."""
+        height = idx.height
+        aundo = res.asset_undo
         bpos = self.block_pos.get(idx.hash)
         if self.db_format == "leveldb" and bpos is not None:
             u = self.undo.pos.get(idx.hash)
@@ -1281,10 +1343,164 @@ class ChainState:
         self.record_confirmations(block, height)
         self._emit("connect_tip", block, idx, undo)
         self._since_flush += 1
+
+    def _flush_if_due(self) -> None:
         if self._since_flush >= self.flush_interval or self._check_for_pruning or \
                 self.coins.dirty * COIN_CACHE_ENTRY_BYTES > self.coins_cache_bytes:
             self.flush()
-        return ValidationState()
+
+    # ------------------------------------------------------------------ -gpusigwindow
+    def _connect_windowed(self, path, connected):
+        """`_activate`'s walk over `path` (oldest first) with the signatures of consecutive blocks
+        verified together. Blocks are connected speculatively (_connect_speculative) and held
+        until their window closes: when its signatures reach -gpusigwindow, when the held block
+        data reaches SIG_WINDOW_MAX_BLOCK_BYTES, at a block for which a listener needs the exact
+        state (_needs_exact_state), at the end of the path or of the stored data, or at a block
+        that fails its speculative half. A closed window is verified in one device
+        pass and its blocks are made final in order (_connect_final); nothing of a block is
+        visible outside the lock before that, and no flush falls inside an open window. The blocks
+        made final are appended to `connected`. -> (idx, state) of the block to invalidate (the
+        UTXO set is then at its parent), or None. On an exception every block still speculative
+        is rolled back before it propagates."""
+        blocks: dict = {}  # block data read ahead, by hash
+        if self.gpu_signatures != "on":
+            # GPU_SIG_BATCH_MIN applies to the window's total: a walk whose stored blocks hold fewer
+            # inputs than that (a node at the tip taking small blocks one at a time) has nothing
+            # for the device and goes block by block, exactly as without the flag
+            n_inputs = 0
+            for idx in path:
+                blk = blocks[idx.hash] = self.get_block(idx.hash)
+                if blk is None:
+                    break
+                n_inputs += sum(len(tx.vin) for tx in blk.vtx[1:])
+                if n_inputs >= GPU_SIG_BATCH_MIN:
+                    break
+            if n_inputs < GPU_SIG_BATCH_MIN:
+                for idx in path:
+                    blk = blocks.get(idx.hash)
+                    if blk is None:
+                        break
+                    st = self._connect_one(blk, idx)
+                    if not st.ok:
+                        return idx, st
+                    connected.append((blk, idx))
+                return None
+        held: list = []  # (block, idx, res, undo) of the open window, in block order
+        try:
+            sigs = nbytes = 0
+            for idx in path:
+                blk = blocks.pop(idx.hash, None) or self.get_block(idx.hash)
+                if blk is None:
+                    break  # data not here yet (headers-first): stop at the last complete block
+                st, res, undo = self._connect_speculative(blk, idx, True)
+                if not st.ok:
+                    # the window before it first: an earlier bad signature wins
+                    return self._close_window(held, connected) or (idx, st)
+                held.append((blk, idx, res, undo))
+                sigs += res.num_sigs
+                pos = self.block_pos.get(idx.hash)
+                nbytes += pos.size if pos is not None else blk.total_size(self.params.kawpow_activation_time)
+                # a listener that reads the UTXO set or the asset state at this block's connect_tip
+                # (a reward snapshot due at its height) must find them at exactly this block: it
+                # is the last of its window
+                if sigs >= self.gpu_sig_window or nbytes >= SIG_WINDOW_MAX_BLOCK_BYTES or \
+                        self._needs_exact_state(blk, idx):
+                    bad = self._close_window(held, connected)
+                    if bad is not None:
+                        return bad
+                    sigs = nbytes = 0
+            return self._close_window(held, connected)
+        except BaseException:
+            self._roll_back(held, 0)
+            raise
+
+    def _needs_exact_state(self, block, idx) -> bool:
+        """Whether a listener asks (ValidationInterface.needs_exact_state) to see the UTXO set and
+        the asset state at exactly this block when its connect_tip fires. A listener whose answer
+        fails counts as asking."""
+        for l in list(self.listeners):
+            fn = getattr(l, "needs_exact_state", None)
+            if fn is None:
+                continue
+            try:
+                if fn(block, idx):
+                    return True
+            except Exception as e:
+                log.log_printf(f"validation listener {type(l).__name__}.needs_exact_state failed: {e}")
+                return True
+        return False
+
+    def _roll_back(self, held: list, first: int) -> None:
+        """Disconnect the speculative blocks held[first:], newest first, from their in-memory undo
+        and asset undo, and drop them from `held`."""
+        while len(held) > first:
+            blk, idx, res, undo = held.pop()
+            if not _core.disconnect_block(blk, undo, self.coins, self.assets, res.asset_undo):
+                log.log_printf(f"rollback of {_core.u256_hex(idx.hash)} found an inconsistent UTXO set")
+
+    def _verify_window(self, held: list) -> list[list[bool]]:
+        """CPubKey::Verify's answer for every deferred signature of the held blocks, one list per
+        block. GPU_SIG_BATCH_MIN applies to the window's total."""
+        results = [res for _, _, res, _ in held]
+        total = sum(res.num_sigs for res in results)
+        if total == 0:
+            return [[] for _ in results]
+        if self.gpu_signatures != "on" and total < GPU_SIG_BATCH_MIN:
+            # what a walk leaves over (its last few blocks, or signatures the cache already knew):
+            # too few for a device pass, and no counter moves, as for a block checked on the host
+            return [[bool(_core.secp_verify(*it)) for it in res.sig_items()] for res in results]
+        verify = self.sig_window_verifier
+        if verify is None:
+            from ..ops import sighash
+
+            verify = sighash.verify_window
+        verdicts = verify(results)
+        if [len(v) for v in verdicts] != [res.num_sigs for res in results]:
+            raise RuntimeError("signature window: the verifier did not answer for every signature")
+        for res in results:
+            n_dev = res.num_device_hashes
+            self.sig_stats["gpu_sighashes"] += n_dev
+            self.sig_stats["host_sighashes"] += res.num_sigs - n_dev
+            self.sig_stats["gpu_sighashes_v0"] += res.num_device_v0
+            self.sig_stats["gpu_sighashes_partial"] += res.num_device_partial
+        self.sig_stats["gpu_batches"] += 1
+        self.sig_stats["gpu_sigs"] += total
+        self.sig_stats["gpu_windows"] += 1
+        self.sig_stats["window_blocks"] += len(results)
+        self.sig_stats["window_sigs"] += total
+        return verdicts
+
+    def _close_window(self, held: list, connected):
+        """Verify the held blocks' signatures together; the host re-checks the rejected inputs of
+        each block in block order. All pass: every block is made final in order. Block j fails:
+        the blocks from the newest back to j are disconnected, those before j are made final, and
+        (idx, state) of j is returned for `_activate` to invalidate. `held` is emptied either way."""
+        if not held:
+            return None
+        verdicts = self._verify_window(held)
+        bad = None
+        flags = _core.BLOCK_SCRIPT_VERIFY_FLAGS
+        for j, (blk, idx, res, undo) in enumerate(held):
+            for t, i in sorted({res.sig_at[k] for k, v in enumerate(verdicts[j]) if not v}):
+                value, spk, _, _ = _core.block_undo_coin(undo, t, i)
+                self.sig_stats["host_rechecks"] += 1
+                ok, err = _core.verify_input_host(blk, t, i, value, spk, flags)
+                if not ok:
+                    bad = (idx, ValidationState.invalid(f"mandatory-script-verify-flag-failed ({err})", 100))
+                    break
+            if bad is not None:
+                self.sig_stats["window_rollbacks"] += 1
+                self._roll_back(held, j)
+                break
+        # from here on the UTXO set holds exactly the blocks of `held`, all verified. A block leaves
+        # `held` before it is made final: one whose final half fails midway stays connected, as on
+        # the per-block path, and is never rolled back with its best block already set
+        while held:
+            blk, idx, res, undo = held.pop(0)
+            self._connect_final(blk, idx, res, undo)
+            connected.append((blk, idx))
+        self._flush_if_due()
+        return bad
 
     def flush(self) -> None:
         """FlushStateToDisk: write the UTXO snapshot (atomically) if anything changed."""

@@ -532,6 +532,43 @@ void bind_script(py::module_& m) {
         }
         return pyb(out);
     }, "host model of sighash_gather_batch: SHA256d of each job's four arena segments, 32 bytes per job");
+    // ---- a window of consecutive blocks as one batch (-gpusigwindow)
+    m.attr("SIG_WINDOW_RECORD_BYTES") = sizeof(SigWindowRecord);
+    m.attr("SIG_WINDOW_NONE") = SIG_WINDOW_NONE;
+    m.attr("SIG_WINDOW_ARENA_LIMIT") = SIG_WINDOW_ARENA_LIMIT;
+    m.def("sig_window_pack", [](const py::list& results, py::object arena_limit) {
+        std::vector<const ConnectResult*> rs;
+        for (auto r : results) rs.push_back(&r.cast<const ConnectResult&>());
+        const u64 limit = arena_limit.is_none() ? SIG_WINDOW_ARENA_LIMIT : arena_limit.cast<u64>();
+        SigWindowPack p;
+        {
+            py::gil_scoped_release rel;
+            p = pack_sig_window(rs, limit);
+        }
+        const bool var = p.mode == SigWindowMode::ALL_FORMS;
+        return py::make_tuple(
+            int(p.mode), pyb(p.arena),
+            py::bytes(reinterpret_cast<const char*>(p.segs.data()), p.segs.size() * sizeof(SighashSeg)),
+            var ? py::bytes(reinterpret_cast<const char*>(p.var_jobs.data()), p.var_jobs.size() * sizeof(SighashVarJob))
+                : py::bytes(reinterpret_cast<const char*>(p.jobs.data()), p.jobs.size() * sizeof(SighashJob)),
+            py::bytes(reinterpret_cast<const char*>(p.secp_jobs.data()), p.secp_jobs.size() * sizeof(SecpVerifyJob)),
+            p.sig_begin, p.device_jobs, p.host_jobs);
+    }, py::arg("results"), py::arg("arena_limit") = py::none(),
+       "(mode, arena, SighashSeg table, job table, SecpVerifyJob array, sig_begin, device-hashed count, host-hashed "
+       "count) of consecutive blocks' ConnectResults as one batch for ops/sighash.verify_window. mode 0: hashes from "
+       "the host (no arena, no job table); 1: defer_sighash (SighashJob table); 2: defer_all_forms (SighashVarJob "
+       "table over the segment table). Every index is moved by its block's base; block b owns signatures "
+       "[sig_begin[b], sig_begin[b+1]). ValueError on results of different modes; an arena that reaches arena_limit "
+       "(default SIG_WINDOW_ARENA_LIMIT) is refused");
+    m.def("sig_window_verdicts_model", [](const std::vector<u32>& verdicts, const std::vector<u32>& sig_begin) {
+        if (sig_begin.empty()) throw std::invalid_argument("signature window: empty prefix table");
+        const std::vector<SigWindowRecord> r =
+            sig_window_verdicts_model(verdicts.data(), verdicts.size(), sig_begin.data(), sig_begin.size() - 1);
+        return py::bytes(reinterpret_cast<const char*>(r.data()), r.size() * sizeof(SigWindowRecord));
+    }, py::arg("verdicts"), py::arg("sig_begin"),
+       "host model of sig_window_verdicts: per block (n_valid, n_invalid, n_ask_host, first_not_valid) as 4 "
+       "little-endian u32, first_not_valid relative to the block (SIG_WINDOW_NONE if every verdict is 1); a verdict "
+       "other than 0, 1 or 2 counts as invalid");
     m.def("connect_block", [](const Block& block, int height, CoinsView& view, bool check_scripts, bool defer_sigs,
                               py::object mtp_at, int64_t block_mtp, u32 flags, int threads, assets::State* asset_state,
                               const assets::Flags& asset_flags, const py::bytes& block_hash, bool sigcache,

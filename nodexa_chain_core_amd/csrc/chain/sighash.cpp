@@ -263,4 +263,111 @@ Bytes sighash_var_model(const Bytes& arena, const SighashSeg* segs, size_t n_seg
     return out;
 }
 
+SigWindowMode sig_window_mode(const ConnectResult& res) {
+    if (res.all_forms) return SigWindowMode::ALL_FORMS;
+    return res.templates.empty() ? SigWindowMode::HOST_HASH : SigWindowMode::LEGACY_ALL;
+}
+
+SigWindowPack pack_sig_window(const std::vector<const ConnectResult*>& results, u64 arena_limit) {
+    SigWindowPack out;
+    out.sig_begin.reserve(results.size() + 1);
+    out.sig_begin.push_back(0);
+    bool have_mode = false;
+    auto check_arena = [&](const Bytes& a) {  // before a block's arena joins the window's
+        if (u64(out.arena.size()) + a.size() >= arena_limit)
+            throw std::length_error("signature window: the arena reaches the 32-bit offset limit");
+    };
+    for (const ConnectResult* r : results) {
+        const ConnectResult& res = *r;
+        const u32 sig_base = out.sig_begin.back();
+        if (u64(sig_base) + res.sigs.size() >= (u64(1) << 31))
+            throw std::length_error("signature window: too many signatures");
+        out.sig_begin.push_back(sig_base + u32(res.sigs.size()));
+        if (res.sigs.empty()) continue;
+        const SigWindowMode mode = sig_window_mode(res);
+        if (have_mode && mode != out.mode)
+            throw std::invalid_argument("signature window: blocks connected with different -gpusighash modes");
+        const bool first = !have_mode;  // the first block with signatures
+        out.mode = mode;
+        have_mode = true;
+        const u32 arena_base = u32(out.arena.size());
+        if (mode == SigWindowMode::HOST_HASH) {
+            for (const PendingSig& p : res.sigs) {
+                if (p.device_hash) throw std::invalid_argument("signature window: a deferred hash without its mode");
+                SecpVerifyJob sj;
+                secp::pack_verify_job(p.pubkey.data(), p.pubkey.size(), p.sig.data(), p.sig.size(), p.msg.data, sj);
+                out.secp_jobs.push_back(sj);
+            }
+            out.host_jobs += res.sigs.size();
+        } else if (mode == SigWindowMode::LEGACY_ALL) {
+            SighashPack p = pack_sighash(res);
+            check_arena(p.arena);
+            if (first) {  // every base is 0: the block's tables are the window's so far, moved not copied
+                out.arena = std::move(p.arena);
+                out.jobs = std::move(p.jobs);
+                out.secp_jobs = std::move(p.secp_jobs);
+                out.device_jobs = p.device_jobs;
+                out.host_jobs = p.host_jobs;
+                continue;
+            }
+            out.arena.insert(out.arena.end(), p.arena.begin(), p.arena.end());
+            for (SighashJob j : p.jobs) {
+                for (int s = 0; s < SIGHASH_SEGMENTS; ++s) j.off[s] += arena_base;
+                j.out_index += sig_base;
+                out.jobs.push_back(j);
+            }
+            out.secp_jobs.insert(out.secp_jobs.end(), p.secp_jobs.begin(), p.secp_jobs.end());
+            out.device_jobs += p.device_jobs;
+            out.host_jobs += p.host_jobs;
+        } else {
+            SighashVarPack p = pack_sighash_var(res);
+            check_arena(p.arena);
+            if (first) {
+                out.arena = std::move(p.arena);
+                out.segs = std::move(p.segs);
+                out.var_jobs = std::move(p.jobs);
+                out.secp_jobs = std::move(p.secp_jobs);
+                out.device_jobs = p.device_jobs;
+                out.host_jobs = p.host_jobs;
+                continue;
+            }
+            out.arena.insert(out.arena.end(), p.arena.begin(), p.arena.end());
+            const u64 seg_base = out.segs.size();
+            if (seg_base + p.segs.size() > 0xffffffffULL) throw std::length_error("signature window: too many segments");
+            for (SighashSeg g : p.segs) {
+                g.off += arena_base;
+                out.segs.push_back(g);
+            }
+            for (SighashVarJob j : p.jobs) {
+                j.first_seg += u32(seg_base);
+                j.out_index += sig_base;
+                out.var_jobs.push_back(j);
+            }
+            out.secp_jobs.insert(out.secp_jobs.end(), p.secp_jobs.begin(), p.secp_jobs.end());
+            out.device_jobs += p.device_jobs;
+            out.host_jobs += p.host_jobs;
+        }
+    }
+    return out;
+}
+
+std::vector<SigWindowRecord> sig_window_verdicts_model(const u32* verdicts, size_t n, const u32* sig_begin, size_t nb) {
+    for (size_t b = 0; b < nb; ++b)
+        if (sig_begin[b] > sig_begin[b + 1]) throw std::invalid_argument("signature window: prefix offsets decrease");
+    if (nb && sig_begin[nb] > n) throw std::invalid_argument("signature window: prefix offsets pass the verdicts");
+    std::vector<SigWindowRecord> out(nb);
+    for (size_t b = 0; b < nb; ++b) {
+        SigWindowRecord r{0, 0, 0, SIG_WINDOW_NONE};
+        for (u32 i = sig_begin[b]; i < sig_begin[b + 1]; ++i) {
+            const u32 v = verdicts[i];
+            if (v == 1) ++r.n_valid;
+            else if (v == 2) ++r.n_ask_host;
+            else ++r.n_invalid;
+            if (v != 1 && r.first_not_valid == SIG_WINDOW_NONE) r.first_not_valid = i - sig_begin[b];
+        }
+        out[b] = r;
+    }
+    return out;
+}
+
 }  // namespace nodexa

@@ -72,4 +72,35 @@ void sighash_var_check(size_t arena_len, const SighashSeg* segs, size_t n_segs, 
 // bytes each, in job order.
 Bytes sighash_var_model(const Bytes& arena, const SighashSeg* segs, size_t n_segs, const SighashVarJob* jobs, size_t n);
 
+// ---- a window of consecutive blocks as one batch (-gpusigwindow; hip/kernels/sig_window.hip)
+//
+// pack_sig_window runs every result through the packer of its mode and concatenates the outputs:
+// arena offsets move by the block's arena base, first_seg by its segment base, out_index by its
+// signature base, so the tables are what sighash_gather_batch / sighash_gather_var and
+// secp_verify_batch take for a single block. Block b owns signatures [sig_begin[b], sig_begin[b+1]).
+enum class SigWindowMode { HOST_HASH = 0, LEGACY_ALL = 1, ALL_FORMS = 2 };
+// HOST_HASH: connected with defer_sigs alone; LEGACY_ALL: with defer_sighash; ALL_FORMS: with
+// defer_all_forms. A result without signatures takes part in a window of any mode.
+SigWindowMode sig_window_mode(const ConnectResult& res);
+// Offsets are 32-bit: a window whose arena plus SIGHASH_ARENA_SLACK would reach 2^31 bytes is refused.
+constexpr u64 SIG_WINDOW_ARENA_LIMIT = (u64(1) << 31) - SIGHASH_ARENA_SLACK;
+struct SigWindowPack {
+    SigWindowMode mode = SigWindowMode::HOST_HASH;  // of the results that have signatures
+    Bytes arena;
+    std::vector<SighashSeg> segs;          // ALL_FORMS
+    std::vector<SighashJob> jobs;          // LEGACY_ALL
+    std::vector<SighashVarJob> var_jobs;   // ALL_FORMS
+    std::vector<SecpVerifyJob> secp_jobs;
+    std::vector<u32> sig_begin;            // results.size() + 1
+    size_t device_jobs = 0, host_jobs = 0;
+};
+// Throws std::invalid_argument on results of different modes, std::length_error on an arena that
+// reaches `arena_limit` bytes (lower than the real limit only in tests).
+SigWindowPack pack_sig_window(const std::vector<const ConnectResult*>& results,
+                              u64 arena_limit = SIG_WINDOW_ARENA_LIMIT);
+
+// The definition of sig_window_verdicts: one SigWindowRecord per block over the verifier's
+// verdicts. Throws std::invalid_argument on a prefix table that decreases or passes n.
+std::vector<SigWindowRecord> sig_window_verdicts_model(const u32* verdicts, size_t n, const u32* sig_begin, size_t nb);
+
 }  // namespace nodexa

@@ -189,6 +189,23 @@ struct SighashVarParams {
     uint32_t n_segs;
 };
 
+// Per-block summary of a window's signature verdicts (sig_window.hip sig_window_verdicts): the
+// verifier's out[] holds the signatures of nb consecutive blocks back to back, block b owning
+// [sig_begin[b], sig_begin[b + 1]) (possibly none). One record per block; a verdict other than
+// 0, 1 or 2 counts as invalid.
+#define SIG_WINDOW_NONE 0xffffffffu
+struct SigWindowRecord {
+    uint32_t n_valid, n_invalid, n_ask_host;
+    uint32_t first_not_valid;        // relative to the block's first signature; SIG_WINDOW_NONE if all are valid
+};
+struct SigWindowParams {
+    const uint32_t* verdicts;        // secp_verify_batch's out[], sig_begin[nb] entries
+    const uint32_t* sig_begin;       // nb + 1 non-decreasing prefix offsets
+    struct SigWindowRecord* records; // nb
+    uint32_t nb;
+    uint32_t pad;
+};
+
 // Batch verification of packed Equihash(200,9) solutions (equihash.hip eq_verify).
 #define EQ_SOL_WORDS 336  // 1344 bytes = 512 x 21-bit big-endian indices
 struct EquihashVerifyParams {

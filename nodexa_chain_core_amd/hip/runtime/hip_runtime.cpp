@@ -660,6 +660,23 @@ PYBIND11_MODULE(_hip, m) {
         k.launch_bytes(dim3((n + 255) / 256), dim3(256), 0, as_stream(stream), &p, sizeof(p));
     });
 
+    // ---- per-block records of a window's verdicts (sig_window.hip): one wave64 per block. The
+    // caller has checked the prefix table: nb + 1 non-decreasing offsets, the last one no larger
+    // than the verdict array; `records` is 16-byte aligned.
+    m.attr("SIG_WINDOW_RECORD_BYTES") = sizeof(SigWindowRecord);
+    m.def("launch_sig_window_verdicts", [](const Kernel& k, uintptr_t verdicts, uintptr_t sig_begin, uint32_t nb,
+                                           uintptr_t records, uintptr_t stream) {
+        if (nb == 0) return;
+        if (!verdicts || !sig_begin || !records) throw std::invalid_argument("sig_window: null table");
+        if (records % 16) throw std::invalid_argument("sig_window: records not 16-byte aligned");
+        SigWindowParams p{};
+        p.verdicts = reinterpret_cast<const uint32_t*>(verdicts);
+        p.sig_begin = reinterpret_cast<const uint32_t*>(sig_begin);
+        p.records = reinterpret_cast<SigWindowRecord*>(records);
+        p.nb = nb;
+        k.launch_bytes(dim3((nb + 3) / 4), dim3(256), 0, as_stream(stream), &p, sizeof(p));
+    });
+
     // ---- Equihash(200,9): one full Wagner solve for `num_inst` inputs, enqueued on `stream`
     m.attr("EQ_BUCKETS") = EQ_BUCKETS;
     m.attr("EQ_WORDS") = EQ_WORDS;

@@ -324,6 +324,9 @@ class Node:
         # GPU batch it has nothing to act on
         self.state.gpu_sighash = a.get_bool("gpusighash", False)
         self.state.gpu_sighash_forms = "all" if (a.get("gpusighash") or "").strip() == "2" else "legacy-all"
+        # -gpusigwindow=<signatures>: with the GPU batch, verify the signatures of consecutive stored
+        # blocks (sync, reindex, a long reorg) in one device pass of about this many; 0 = block by block
+        self.state.gpu_sig_window = max(0, a.get_int("gpusigwindow", 0))
         if self.datadir is not None:  # fee_estimates.dat (src/init.cpp: est_filein), before the mempool
             self.state.load_fee_estimates(os.path.join(self.datadir, "fee_estimates.dat"))
         if self.datadir is not None and a.get_bool("persistmempool", True):  # -persistmempool (LoadMempool)
@@ -927,7 +930,7 @@ class Node:
         for g in out:
             g["intensity"] = svc.window
             g["ranks"] = svc.world_size
-        if out:  # the node's own entry: block validation's GPU batches (-gpusigs, -gpusighash)
+        if out:  # the node's own entry: block validation's GPU batches (-gpusigs, -gpusighash, -gpusigwindow)
             out[0]["block_sigs"] = dict(self.state.sig_stats)
         if out and self.gpus:
             try:

@@ -18,6 +18,12 @@ A block connected with `defer_all_forms=True` leaves every form of both signatur
 through a table of up to SIGHASH_VAR_MAX_SEGMENTS arena ranges and `sighash_gather_var`
 (hip/kernels/sighash_var.hip) hashes them; `digests_var` and `gather_var_into_secp` are that
 kernel on its own, and `verify_block_sigs` takes this path for such a result.
+
+`verify_window` is the same pass over a run of consecutive blocks (-gpusigwindow):
+`_core.sig_window_pack` concatenates the blocks' tables, the gather and the verifier run once over
+all of them, and `sig_window_verdicts` (hip/kernels/sig_window.hip) condenses the verdicts to one
+16-byte record per block, the only thing that comes back while every signature is valid.
+`verdict_records` is that kernel on its own.
 """
 from __future__ import annotations
 
@@ -174,3 +180,110 @@ def verify_block_sigs(res, device: int | None = None) -> list[bool]:
         items = res.sig_items()
         return [bool(_core.secp_verify(*items[k])) if v == 2 else v == 1 for k, v in enumerate(verdicts)]
     return [v == 1 for v in verdicts]
+
+
+# ---------------------------------------------------------------- a window of consecutive blocks
+RECORD_BYTES = _core.SIG_WINDOW_RECORD_BYTES
+NONE = _core.SIG_WINDOW_NONE
+
+
+def _check_sig_begin(sig_begin, n: int) -> np.ndarray:
+    """The prefix table as the kernel reads it; nothing malformed reaches the device."""
+    sb = np.asarray(sig_begin, dtype=np.int64)
+    if sb.ndim != 1 or len(sb) < 1 or sb[0] < 0 or np.any(np.diff(sb) < 0) or sb[-1] > n or n >= 1 << 31:
+        raise ValueError("signature window: the prefix table does not fit the verdicts")
+    return sb.astype(np.uint32)
+
+
+def _launch_records(h, d_out: torch.Tensor, sig_begin: np.ndarray, dev: torch.device, stream) -> torch.Tensor:
+    nb = len(sig_begin) - 1
+    d_begin = torch.from_numpy(sig_begin.view(np.int32).copy()).to(dev)
+    records = torch.empty((nb, RECORD_BYTES // 4), dtype=torch.int32, device=dev)
+    h.launch_sig_window_verdicts(runtime.static_kernel("sig_window", "sig_window_verdicts"), d_out.data_ptr(),
+                                 d_begin.data_ptr(), nb, records.data_ptr(), stream)
+    return records
+
+
+def verdict_records(verdicts, sig_begin, device: int | None = None) -> bytes:
+    """`sig_window_verdicts` on its own: the per-block records of a verdict array, as raw bytes.
+    Equals `_core.sig_window_verdicts_model(verdicts, sig_begin)` byte for byte."""
+    v = np.asarray(verdicts, dtype=np.uint32)
+    sb = _check_sig_begin(sig_begin, len(v))
+    if len(sb) == 1:
+        return b""
+    runtime.require_gpu()
+    dev = _device(device)
+    with torch.cuda.device(dev):
+        # an empty verdict array still gets a valid (unread) buffer
+        d_out = torch.from_numpy(np.concatenate([v, np.zeros(1, np.uint32)]).view(np.int32)).to(dev)
+        rec = _launch_records(runtime.hip(), d_out, sb, dev, runtime.current_stream_handle())
+        return rec.cpu().numpy().tobytes()
+
+
+def _window_pass(results, device: int | None):
+    """One pack, one upload of each table, gather (if any hash is left to the device),
+    secp_verify_batch, sig_window_verdicts: -> (records (nb, 4) uint32, verdicts on the device,
+    sig_begin), or None for a window without signatures, which launches nothing."""
+    mode, arena, segs, jobs, secp_jobs, sig_begin, n_dev, _n_host = _core.sig_window_pack(list(results))
+    n = sig_begin[-1]
+    if n == 0:
+        return None
+    runtime.require_gpu()
+    h = runtime.hip()
+    dev = _device(device)
+    sb = _check_sig_begin(sig_begin, n)
+    with torch.cuda.device(dev):
+        stream = runtime.current_stream_handle()
+        d_secp = torch.frombuffer(bytearray(secp_jobs), dtype=torch.int32).to(dev)
+        out = torch.empty(n, dtype=torch.int32, device=dev)
+        gtab = secp._gen_table(dev)  # uploaded on first use: before the launches, not between them
+        if n_dev and mode == 2:
+            d_arena, d_segs, d_jobs = _upload_var(arena, segs, jobs, n, dev)
+            h.launch_sighash_gather_var(runtime.static_kernel("sighash_var", "sighash_gather_var"), d_arena.data_ptr(),
+                                        d_segs.data_ptr(), len(segs) // SEG_BYTES, d_jobs.data_ptr(), n_dev, 0,
+                                        d_secp.data_ptr(), stream)
+        elif n_dev:
+            d_arena, d_jobs = _upload_jobs(arena, jobs, n, dev)
+            h.launch_sighash_gather(runtime.static_kernel("sighash", "sighash_gather_batch"), d_arena.data_ptr(),
+                                    d_jobs.data_ptr(), n_dev, 0, d_secp.data_ptr(), stream)
+        h.launch_secp_verify(runtime.static_kernel("secp256k1_verify", "secp_verify_batch"), d_secp.data_ptr(), n,
+                             gtab.data_ptr(), out.data_ptr(), stream)
+        records = _launch_records(h, out, sb, dev, stream).cpu().numpy().view(np.uint32)
+    return records, out, sb
+
+
+def window_records(results, device: int | None = None) -> list[tuple[int, int, int, int]]:
+    """The raw per-block records of `verify_window`'s device pass: (n_valid, n_invalid,
+    n_ask_host, first_not_valid) for each result, first_not_valid relative to the block's first
+    signature and SIG_WINDOW_NONE when every verdict is valid."""
+    got = _window_pass(results, device)
+    if got is None:
+        return [(0, 0, 0, NONE) for _ in results]
+    return [tuple(int(x) for x in row) for row in got[0]]
+
+
+@traced("sighash.verify_window")
+def verify_window(results, device: int | None = None) -> list[list[bool]]:
+    """CPubKey::Verify's answer for every deferred signature of a run of consecutive blocks'
+    `connect_block(defer_sigs=True, ...)` results, verified in one device pass: entry b equals what
+    `verify_block_sigs(results[b])` (or `secp.verify_batch(results[b].sig_items())` for a result
+    whose hashes came from the host) returns. All results are of one -gpusighash mode. Only one
+    16-byte record per block comes back; the verdicts of a block are fetched when its record shows
+    one that is not valid, and a verdict 2 is re-checked on the host with the host-computed message."""
+    got = _window_pass(results, device)
+    if got is None:
+        return [[] for _ in results]
+    records, out, sb = got
+    answers = []
+    for b, res in enumerate(results):
+        lo, hi = int(sb[b]), int(sb[b + 1])
+        if records[b][3] == NONE and records[b][0] == hi - lo:
+            answers.append([True] * (hi - lo))
+            continue
+        verdicts = out[lo:hi].cpu().tolist()
+        if 2 in verdicts:
+            items = res.sig_items()
+            answers.append([bool(_core.secp_verify(*items[k])) if v == 2 else v == 1 for k, v in enumerate(verdicts)])
+        else:
+            answers.append([v == 1 for v in verdicts])
+    return answers

@@ -153,6 +153,11 @@ class Rewards(ValidationInterface):
         return True
 
     # ------------------------------------------------------------------ block hooks
+    def needs_exact_state(self, block, index) -> bool:
+        """A snapshot due at this height reads the asset balances in connect_tip: they must be
+        those of exactly this block, also inside a -gpusigwindow walk."""
+        return bool(self.list_requests("", index.height))
+
     def connect_tip(self, block, index, undo: bytes) -> None:
         due = [(n, h) for n, h in self.list_requests("", index.height)]
         if due:

@@ -1,0 +1,318 @@
+#!/usr/bin/env python3
+"""Connecting a run of stored blocks with one GPU signature batch per block against one per window
+(-gpusigwindow).
+
+Two seeded regtest chains of the shapes a syncing node meets: many small blocks (512 blocks of one
+24-input P2PKH transaction) and fewer large ones (64 blocks of one 200-input transaction). Each
+chain's blocks are stored in a fresh chain state without being connected; the timed part is the one
+`_activate` walk that connects them all, which ends in the last verdict download. The settings
+(-gpusigwindow 0, 1024, 4096, 16384, 65536, each with -gpusighash 0 and 2) alternate in one process,
+warm-ups first. Then the three kernels of a window alone, with device events, at the signature
+counts the windows reach; and the single consolidation block of tools/sighash_probe.py through
+verify_window against the per-block call.
+
+--cache DIR keeps the built chains (signing and mining them takes a while on the host) for the next
+run. A GPU tool, not a test: it fails without a GPU. One JSON document on stdout (and in --out).
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import pickle
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+WINDOWS = (0, 1024, 4096, 16384, 65536)
+MODES = (0, 2)
+WITNESS_COMMITMENT_HEADER = b"\x6a\x24\xaa\x21\xa9\xed"
+
+
+def _stats(xs):
+    return {"median_ms": round(statistics.median(xs), 3), "min_ms": round(min(xs), 3), "max_ms": round(max(xs), 3),
+            "runs_ms": [round(x, 3) for x in xs]}
+
+
+def _faster(a, b, name_a, name_b):
+    return (f"{name_a} faster" if max(a) < min(b) else f"{name_b} faster" if max(b) < min(a) else
+            "no difference beyond the spread of the repeats")
+
+
+def _new_state():
+    from nodexa_chain_core_amd.chain.state import REGTEST_KAWPOW_FROM_GENESIS, ChainState, make_params
+
+    st = ChainState(make_params("regtest", REGTEST_KAWPOW_FROM_GENESIS), None)
+    st.gpu_signatures = "off"
+    return st
+
+
+def build_chain(n_blocks: int, n_inputs: int, seed0: int):
+    """-> (coins, raws): the outputs the chain spends, [(txid, n, value, scriptPubKey)], and its
+    serialized blocks. Each block is a mined regtest block on the previous one: the assembler's
+    coinbase and header around one seeded synth_block transaction of `n_inputs` P2PKH inputs."""
+    from nodexa_chain_core_amd import core
+    from nodexa_chain_core_amd.miner.assembler import BlockAssembler
+    from nodexa_chain_core_amd.utils.synth_block import make_consolidation_block
+
+    _core = core()
+    st = _new_state()
+    act = st.params.kawpow_activation_time
+    ctx = _core.get_epoch_context(0)
+    coins, raws = [], []
+    for k in range(n_blocks):
+        synth, view, _, _ = make_consolidation_block(1, n_inputs, seed=seed0 + k)
+        for tx in synth.vtx[1:]:
+            for vin in tx.vin:
+                value, spk, _, _ = view.get(vin.prevout.hash, vin.prevout.n)
+                coins.append((vin.prevout.hash, vin.prevout.n, value, spk))
+                st.coins.add(vin.prevout.hash, vin.prevout.n, value, spk, 1, False)
+        blk = BlockAssembler(st).create_new_block(b"\x51").block
+        blk.vtx = [blk.vtx[0]] + list(synth.vtx[1:])
+        vtx = list(blk.vtx)
+        cb = vtx[0]
+        outs = list(cb.vout)
+        outs[blk.witness_commitment_index()] = _core.TxOut(
+            0, WITNESS_COMMITMENT_HEADER + _core.sha256d(blk.witness_merkle_root() + bytes(32)))
+        cb.vout = outs
+        blk.vtx = [cb] + vtx[1:]
+        h = blk.header
+        h.merkle_root = blk.merkle_root()[0]
+        for n in range(256):  # regtest target 2^255
+            fin, mix = _core.kawpow_hash(ctx, h.height, h.kawpow_header_hash()[::-1], n)
+            if fin[0] < 0x80:
+                h.nonce64, h.mix_hash = n, mix[::-1]
+                break
+        blk.header = h
+        r = st.process_new_block(blk)
+        assert r.ok, r.reject
+        raws.append(blk.serialize(act))
+    return coins, raws
+
+
+def cached_chain(cache, n_blocks, n_inputs, seed0):
+    path = os.path.join(cache, f"chain_{n_blocks}x{n_inputs}_{seed0}.pickle") if cache else None
+    if path and os.path.exists(path):
+        with open(path, "rb") as f:
+            return pickle.load(f)
+    got = build_chain(n_blocks, n_inputs, seed0)
+    if path:
+        os.makedirs(cache, exist_ok=True)
+        with open(path, "wb") as f:
+            pickle.dump(got, f)
+    return got
+
+
+def connect_once(coins, blocks, window: int, mode: int):
+    """One activation walk over the stored chain -> (ms, sig_stats)."""
+    import torch
+
+    st = _new_state()
+    for txid, n, value, spk in coins:
+        st.coins.add(txid, n, value, spk, 1, False)
+    real = st._activate
+    st._activate = lambda: {}  # store only
+    for blk in blocks:
+        r = st.process_new_block(blk, check_pow=False)
+        assert r.ok, r.reject
+    st._activate = real
+    st.gpu_signatures = "on"
+    st.gpu_sig_window = window
+    st.gpu_sighash, st.gpu_sighash_forms = mode >= 1, "all" if mode == 2 else "legacy-all"
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    with st.lock:
+        failed = st._activate()
+    torch.cuda.synchronize()
+    ms = (time.perf_counter() - t0) * 1e3
+    assert not failed and st.height() == len(blocks), (failed, st.height())
+    return ms, dict(st.sig_stats), st.coins.stats()[3]
+
+
+def probe_chain(name, coins, raws, repeats, warmup):
+    from nodexa_chain_core_amd import core
+
+    _core = core()
+    act = _new_state().params.kawpow_activation_time
+    blocks = [_core.Block.deserialize(raw, act) for raw in raws]
+    settings = [(w, m) for m in MODES for w in WINDOWS]
+    runs = {s: [] for s in settings}
+    stats, utxo = {}, set()
+    for i in range(warmup + repeats):
+        for s in settings:
+            ms, st, h = connect_once(coins, blocks, *s)
+            utxo.add(h)
+            if i >= warmup:
+                runs[s].append(ms)
+                stats[s] = st
+    assert len(utxo) == 1  # every setting ends with the same UTXO set
+    n_sigs = stats[settings[0]]["gpu_sigs"]
+    out = {"chain": name, "blocks": len(blocks), "sigs": n_sigs, "block_bytes": sum(len(r) for r in raws), "settings": []}
+    for w, m in settings:
+        base = runs[(0, m)]
+        out["settings"].append(dict(
+            _stats(runs[(w, m)]), gpusigwindow=w, gpusighash=m, device_passes=stats[(w, m)]["gpu_batches"],
+            gpu_windows=stats[(w, m)]["gpu_windows"], gpu_sigs=stats[(w, m)]["gpu_sigs"],
+            speedup_median=round(statistics.median(base) / statistics.median(runs[(w, m)]), 2),
+            verdict=_faster(runs[(w, m)], base, "window", "per block") if w else "baseline"))
+    return out
+
+
+def _time_kernel(launch, warmup, repeats):
+    import torch
+
+    ms = []
+    for i in range(warmup + repeats):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        launch()
+        e1.record()
+        e1.synchronize()
+        if i >= warmup:
+            ms.append(e0.elapsed_time(e1))
+    return ms
+
+
+def probe_kernels(repeats, warmup, n_inputs=24, sizes=(24, 1008, 4080, 16368, 65520)):
+    """Device time of sighash_gather_var, secp_verify_batch and sig_window_verdicts over windows of
+    24-input blocks (every hash left to the device) holding about `sizes` signatures."""
+    import numpy as np
+    import torch
+
+    from nodexa_chain_core_amd import core
+    from nodexa_chain_core_amd.ops import runtime, secp, sighash
+    from nodexa_chain_core_amd.utils.synth_block import make_consolidation_block
+
+    _core = core()
+    h = runtime.hip()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    stream = runtime.current_stream_handle()
+    n_blocks = max(sizes) // n_inputs
+    # few distinct blocks, repeated: the kernels do not care, and signing 65,536 inputs takes minutes
+    distinct = []
+    for k in range(16):
+        blk, view, height, _ = make_consolidation_block(1, n_inputs, seed=9000 + k)
+        res, _ = _core.connect_block(blk, height, view, True, True, None, 0, _core.BLOCK_SCRIPT_VERIFY_FLAGS, 1,
+                                     defer_sighash=True, defer_all_forms=True)
+        assert res.ok and res.num_sigs == n_inputs
+        distinct.append(res)
+    out = []
+    for n in sizes:
+        results = [distinct[k % len(distinct)] for k in range(n // n_inputs)]
+        mode, arena, segs, jobs, secp_jobs, sig_begin, n_dev, _ = _core.sig_window_pack(results)
+        total = sig_begin[-1]
+        d_arena, d_segs, d_jobs = sighash._upload_var(arena, segs, jobs, total, dev)
+        d_secp = torch.frombuffer(bytearray(secp_jobs), dtype=torch.int32).to(dev)
+        verdicts = torch.empty(total, dtype=torch.int32, device=dev)
+        gtab = secp._gen_table(dev)
+        sb = np.asarray(sig_begin, dtype=np.uint32)
+        d_begin = torch.from_numpy(sb.view(np.int32).copy()).to(dev)
+        records = torch.empty((len(results), 4), dtype=torch.int32, device=dev)
+        kg = runtime.static_kernel("sighash_var", "sighash_gather_var")
+        kv = runtime.static_kernel("secp256k1_verify", "secp_verify_batch")
+        kr = runtime.static_kernel("sig_window", "sig_window_verdicts")
+        gather = _time_kernel(lambda: h.launch_sighash_gather_var(
+            kg, d_arena.data_ptr(), d_segs.data_ptr(), len(segs) // sighash.SEG_BYTES, d_jobs.data_ptr(), n_dev, 0,
+            d_secp.data_ptr(), stream), warmup, repeats)
+        verify = _time_kernel(lambda: h.launch_secp_verify(kv, d_secp.data_ptr(), total, gtab.data_ptr(),
+                                                           verdicts.data_ptr(), stream), warmup, repeats)
+        recs = _time_kernel(lambda: h.launch_sig_window_verdicts(kr, verdicts.data_ptr(), d_begin.data_ptr(),
+                                                                 len(results), records.data_ptr(), stream),
+                            warmup, repeats)
+        assert records.cpu().numpy().view(np.uint32).tolist() == [[n_inputs, 0, 0, 0xffffffff]] * len(results)
+        out.append({"blocks": len(results), "sigs": total, "arena_bytes": len(arena),
+                    "sighash_gather_var": _stats(gather), "secp_verify_batch": _stats(verify),
+                    "sig_window_verdicts": _stats(recs), "record_bytes": 16 * len(results), "verdict_bytes": 4 * total})
+    return out
+
+
+def probe_single_block(repeats, warmup, threads, n_txs=60, n_inputs=200):
+    """The consolidation block of tools/sighash_probe.py: connect + verdicts through the per-block
+    call and through a window of that one block, alternated."""
+    from nodexa_chain_core_amd import core
+    from nodexa_chain_core_amd.ops import secp, sighash
+    from nodexa_chain_core_amd.utils.synth_block import make_consolidation_block
+
+    _core = core()
+    blk, view, height, info = make_consolidation_block(n_txs, n_inputs, seed=7)
+    flags = _core.BLOCK_SCRIPT_VERIFY_FLAGS
+
+    def run(mode, window):
+        t0 = time.perf_counter()
+        res, undo = _core.connect_block(blk, height, view, True, True, None, 0, flags, threads,
+                                        defer_sighash=mode > 0, defer_all_forms=mode == 2)
+        assert res.ok, res.reject
+        if window:
+            verdicts = sighash.verify_window([res])[0]
+        else:
+            verdicts = sighash.verify_block_sigs(res) if mode else secp.verify_batch(res.sig_items())
+        ms = (time.perf_counter() - t0) * 1e3
+        assert all(verdicts) and len(verdicts) == info["sigs"]
+        assert _core.disconnect_block(blk, undo, view)
+        return ms
+
+    settings = [(m, w) for m in (0, 1, 2) for w in (False, True)]
+    runs = {s: [] for s in settings}
+    for i in range(warmup + repeats):
+        for s in settings:
+            ms = run(*s)
+            if i >= warmup:
+                runs[s].append(ms)
+    return [{"gpusighash": m, "sigs": info["sigs"], "per_block": _stats(runs[(m, False)]),
+             "window_of_one": _stats(runs[(m, True)]),
+             "verdict": _faster(runs[(m, True)], runs[(m, False)], "window", "per block")} for m in (0, 1, 2)]
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--threads", type=int, default=min(16, os.cpu_count() or 1))
+    ap.add_argument("--small", default="512x24", help="blocks x inputs of the small-block chain")
+    ap.add_argument("--large", default="64x200", help="blocks x inputs of the large-block chain")
+    ap.add_argument("--cache", default=None, help="directory that keeps the built chains")
+    ap.add_argument("--build-only", action="store_true", help="build (and cache) the chains, then stop: needs no GPU")
+    ap.add_argument("--sections", default="chains,kernels,single", help="which parts to run")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    sections = set(a.sections.split(","))
+    from nodexa_chain_core_amd import _build
+
+    _build.build_core()
+    from nodexa_chain_core_amd import core
+
+    core().sigcache_set_max_bytes(0)  # as for blocks relayed by peers: no signature known from the mempool
+    chains = []
+    for name, spec, seed0 in (("small blocks", a.small, 100_000),
+                              ("large blocks", a.large, 200_000)) if "chains" in sections else ():
+        n_blocks, n_inputs = (int(x) for x in spec.split("x"))
+        chains.append((f"{name} ({n_blocks} x {n_inputs} inputs)", *cached_chain(a.cache, n_blocks, n_inputs, seed0)))
+    if a.build_only:
+        return 0
+    import torch
+
+    if not torch.cuda.is_available():
+        print("sig_window_probe: no GPU present", file=sys.stderr)
+        return 2
+    _build.build_all()
+    doc = {"device": torch.cuda.get_device_name(0), "repeats": a.repeats, "warmup": a.warmup, "chains": []}
+    for name, coins, raws in chains:
+        doc["chains"].append(probe_chain(name, coins, raws, a.repeats, a.warmup))
+        print(json.dumps(doc["chains"][-1]), flush=True)
+    if "kernels" in sections:
+        doc["kernels"] = probe_kernels(a.repeats, a.warmup)
+        print(json.dumps(doc["kernels"]), flush=True)
+    if "single" in sections:
+        doc["single_block"] = probe_single_block(a.repeats, a.warmup, a.threads)
+        print(json.dumps(doc["single_block"]), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(doc, f, indent=1)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
