@@ -56,6 +56,8 @@ def chunk_span(first: int, count: int, chunk_items: int = DAG_CHUNK_ITEMS) -> tu
 
 # hashes per 16-lane row of ethash_hash_batch (EH_HASHES in hip/kernels/ethash_hashimoto.hip)
 EH_HASHES = 2
+# entries of ethash_search's hit list: a window with more hits than this is read back in full
+ETHASH_MAX_HITS = 1024
 
 
 class DeviceEpoch:
@@ -316,19 +318,22 @@ class DeviceEpoch:
         return [(raw[i * 64 + 32:i * 64 + 64], raw[i * 64:i * 64 + 32]) for i in range(n)]
 
     def ethash_search(self, header_hash: bytes, boundary: bytes, start_nonce: int, iterations: int,
-                      window: int = 1 << 22) -> tuple[int, bytes, bytes] | None:
+                      window: int = 1 << 22, max_hits: int = ETHASH_MAX_HITS) -> tuple[int, bytes, bytes] | None:
         """ethash::search (src/crypto/ethash/lib/ethash/ethash.cpp:326-350): the first nonce in
         [start_nonce, start_nonce + iterations) whose classic Ethash final hash is <= boundary, as
         (nonce, final_hash, mix_hash), or None. Nonces run on the device in windows of `window`
         (job i = start + i, no host-side job list); the final kernel appends each hit and the
-        lowest one of the first window that has any is the answer."""
+        lowest one of the first window that has any is the answer. The hit list holds `max_hits`
+        indices; of a window with more hits every final hash is read back and compared on the host."""
         if not self.built or self.dag is None:
             raise RuntimeError("ethash_search needs the built DAG")
         if len(header_hash) != 32 or len(boundary) != 32:
             raise ValueError("32-byte header hash and boundary")
         h = runtime.hip()
         ks = [runtime.static_kernel("ethash_hashimoto", f"ethash_{x}_batch") for x in ("seed", "mix", "final")]
-        max_hits = 1024
+        max_hits = int(max_hits)
+        if max_hits < 1:
+            raise ValueError("the hit list needs at least one entry")
         with torch.cuda.device(self.device):
             w = max(1, min(int(window), int(iterations)))
             out = torch.empty(w * 16, dtype=torch.int32, device=self.device)

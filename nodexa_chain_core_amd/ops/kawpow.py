@@ -207,11 +207,12 @@ class KawpowSearcher:
     @traced("kawpow.search")
     def search(self, header_hash: bytes, start_nonce: int, num_nonces: int, boundary: bytes) -> list[Share]:
         """All shares in [start, start+num) with final <= boundary (bit-exact, host-checked).
-        The launch is rounded up to whole workgroups; shares past the window are dropped."""
+        The launch is rounded up to whole workgroups; shares past the window are dropped. Nonces
+        count mod 2^64, as the kernel's do: a window may run past 2^64 - 1 and go on from 0."""
         padded = -(-num_nonces // self.block) * self.block
         self.launch(header_hash, start_nonce, padded, target_prefix(boundary))
-        end = start_nonce + num_nonces
-        return [s for s in self.collect() if s.nonce < end and _core.hash_le(s.final_hash, boundary)]
+        return [s for s in self.collect()
+                if (s.nonce - start_nonce) & 0xFFFFFFFFFFFFFFFF < num_nonces and _core.hash_le(s.final_hash, boundary)]
 
     def hash_batch(self, header_hashes: list[bytes], nonces: list[int]) -> list[tuple[bytes, bytes]]:
         """(final, mix) for each (header, nonce) at this searcher's block height."""

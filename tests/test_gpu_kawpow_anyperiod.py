@@ -4,10 +4,10 @@ static resident-DAG batch kernel kawpow_verify_dag (every nonce of the window, f
 with the kernel's 64-bit prefix rule), single hashes by the CPU golden model."""
 import threading
 
-import numpy as np
 import pytest
 
 from kawpow_vectors import VECTORS
+from search_oracle import as_set, boundary_for, clear_cache, oracle_window
 
 pytestmark = pytest.mark.gpu
 
@@ -21,11 +21,6 @@ ORACLE_COUNTS = {0: 6, 3: 11, 49: 13, 50: 13, 99: 7, 7499: 16}
 ORACLE_COUNT_BIG = 11                     # height 50, 16 granules, PREFIX_1024
 ORACLE_COUNT_E385 = 9                     # height 2,887,500, 2 granules, PREFIX_128
 E385_HEIGHT = 2_887_500
-
-
-def boundary_for(prefix: int) -> bytes:
-    """A 256-bit boundary whose full compare equals the 64-bit prefix test."""
-    return prefix.to_bytes(8, "big") + b"\xff" * 24
 
 
 def build_epoch(core, epoch):
@@ -43,41 +38,6 @@ def build_epoch(core, epoch):
 @pytest.fixture(scope="module")
 def epoch0(gpu, core):
     return build_epoch(core, 0)
-
-
-_oracle_cache: dict[tuple, list] = {}
-
-
-def oracle_window(ep, height, start, n, prefix, header=HEADER):
-    """[(nonce, mix, final)] of [start, start + n) with bswap64(final[0..1]) <= prefix, hashed by
-    kawpow_verify_dag (one job per 16-lane group, program and mix in LDS). Computed once per window."""
-    key = (ep.epoch, height, start, n, prefix, header)
-    if key not in _oracle_cache:
-        import torch
-
-        from nodexa_chain_core_amd.ops import runtime
-        from nodexa_chain_core_amd.ops import verify as V
-
-        jobs = V._pack_jobs([height] * n, [header] * n, [start + i for i in range(n)])
-        with torch.cuda.device(ep.device):
-            dj, progs, nprog, jp = V._grouped(jobs, ep.device)
-            res = torch.empty(n * 16, dtype=torch.int32, device=ep.device)
-            runtime.hip().launch_kawpow_verify_dag(
-                runtime.static_kernel("kawpow_verify_light", "kawpow_verify_dag"), ep.dag.data_ptr(), ep.items2048,
-                ep.l1.data_ptr(), dj.data_ptr(), progs.data_ptr(), nprog, jp.data_ptr(), n, res.data_ptr(),
-                runtime.current_stream_handle())
-            rows = res.cpu().numpy().view(np.uint8).reshape(n, 64)
-        out = []
-        for i in range(n):
-            fin = rows[i, 32:].tobytes()
-            if int.from_bytes(fin[:8], "big") <= prefix:
-                out.append((start + i, rows[i, :32].tobytes(), fin))
-        _oracle_cache[key] = out
-    return list(_oracle_cache[key])
-
-
-def as_set(shares):
-    return {(s.nonce, s.mix_hash, s.final_hash) for s in shares}
 
 
 def check_window(core, ep, height, granules, prefix, expect_count):
@@ -166,7 +126,7 @@ def test_dag_above_4gib(core, gpu):
         assert ep.dag_bytes >= 1 << 32
         check_window(core, ep, E385_HEIGHT, 2, PREFIX_128, ORACLE_COUNT_E385)
     finally:
-        _oracle_cache.clear()
+        clear_cache()
         del ep
         torch.cuda.empty_cache()
 
