@@ -17,7 +17,9 @@ result is only trusted where it cannot differ from the reference: any input whos
 batch rejects is re-run on the host, and a block whose deferred run fails is re-connected with
 host checks (`_connect_one`). With -gpusigwindow the batch covers a run of consecutive blocks
 instead: they are connected speculatively and made final, in order, once the run has verified
-(`_connect_windowed`).
+(`_connect_windowed`). With -gpumultisig a CHECKMULTISIG leaves every candidate (signature, key)
+pair in the batch and the device resolves the pairing, so a multisig input signed by any subset of
+its keys is not one of the inputs the batch rejects.
 
 Storage (-dbformat, `detect_db_format`): by default the block index and the UTXO set live in
 LevelDB-format stores with the reference's keys — blocks/index/ (BlockTreeDB: 'b' CDiskBlockIndex
@@ -277,16 +279,26 @@ class ChainState:
         # gpu_windows / window_blocks / window_sigs: device passes over a window of blocks
         # (-gpusigwindow), the blocks and signatures they covered; window_rollbacks: windows that
         # were rolled back to a block whose signatures failed
+        # gpu_multisig_groups / gpu_multisig_entries: CHECKMULTISIGs whose pairing the batch resolved
+        # (-gpumultisig) and the entries of gpu_sigs they account for
         self.sig_stats = {"gpu_batches": 0, "gpu_sigs": 0, "host_rechecks": 0, "gpu_sighashes": 0,
                           "host_sighashes": 0, "gpu_sighashes_v0": 0, "gpu_sighashes_partial": 0,
-                          "gpu_windows": 0, "window_blocks": 0, "window_sigs": 0, "window_rollbacks": 0}
+                          "gpu_windows": 0, "window_blocks": 0, "window_sigs": 0, "window_rollbacks": 0,
+                          "gpu_multisig_groups": 0, "gpu_multisig_entries": 0}
         # -gpusigwindow=<signatures>: with the GPU batch, _activate connects consecutive blocks
         # speculatively and verifies their signatures in one device pass of about this many (0: off,
         # every block on its own)
         self.gpu_sig_window = 0
         # what verifies a window: list of ConnectResults -> one list of verdicts per result. None:
-        # ops.sighash.verify_window, on a GPU; anything else is called without asking for one
+        # ops.sighash.verify_window, on a GPU; anything else is called without asking for one. With
+        # -gpumultisig the results carry CHECKMULTISIG groups (res.sig_groups) and the verifier
+        # returns resolved answers: every entry of a group is True exactly when the group's walk
+        # (_core.sig_group_resolve_model over the per-entry verdicts) succeeds
         self.sig_window_verifier = None
+        # -gpumultisig=1: with the GPU batch, a CHECKMULTISIG leaves every candidate (signature, key)
+        # pair in the batch and the device runs the pairing walk, so an input signed by any subset
+        # of its keys needs no host re-check (0: the walk pairs signature k with key k only)
+        self.gpu_multisig = 0
         self.db_format = detect_db_format(datadir, db_format)
         self.coins_db = None
         self._coins_obf = b""
@@ -1275,6 +1287,11 @@ class ChainState:
         gpu_hash = gpu and self.gpu_sighash  # only with the GPU batch: the host path hashes as it verifies
 
         def connect(defer: bool):
+            if defer and self.gpu_multisig:
+                return _core.connect_block(block, height, self.coins, check_scripts, defer, mtp_at, mtp_prev, flags,
+                                           par, self.assets, aflags, idx.hash, defer_sighash=bool(gpu_hash),
+                                           defer_all_forms=bool(gpu_hash) and self.gpu_sighash_forms == "all",
+                                           defer_multisig=True)
             if defer and gpu_hash:
                 return _core.connect_block(block, height, self.coins, check_scripts, defer, mtp_at, mtp_prev, flags,
                                            par, self.assets, aflags, idx.hash, defer_sighash=True,
@@ -1302,10 +1319,11 @@ class ChainState:
                 self.sig_stats["gpu_sighashes_v0"] += res.num_device_v0
                 self.sig_stats["gpu_sighashes_partial"] += res.num_device_partial
             else:
-                verdicts = secp.verify_batch(res.sig_items())
+                verdicts = secp.verify_batch(res.sig_items(), groups=res.sig_group_table())
                 self.sig_stats["host_sighashes"] += len(verdicts)
             self.sig_stats["gpu_batches"] += 1
             self.sig_stats["gpu_sigs"] += len(verdicts)
+            self._count_groups(res)
             for t, i in sorted({res.sig_at[k] for k, v in enumerate(verdicts) if not v}):
                 value, spk, _, _ = _core.block_undo_coin(undo, t, i)
                 self.sig_stats["host_rechecks"] += 1
@@ -1318,6 +1336,11 @@ class ChainState:
             _core.disconnect_block(block, undo, self.coins, self.assets, aundo)
             return ValidationState.invalid(reason, dos), res, undo
         return ValidationState(), res, undo
+
+    def _count_groups(self, res) -> None:
+        for _first, m, n in res.sig_groups:
+            self.sig_stats["gpu_multisig_groups"] += 1
+            self.sig_stats["gpu_multisig_entries"] += m * (n - m + 1)
 
     def _connect_final(self, block, idx, res, undo) -> None:
         """The half of ConnectTip that others see: the undo and index records, the UTXO set's best
@@ -1448,7 +1471,9 @@ class ChainState:
         if self.gpu_signatures != "on" and total < GPU_SIG_BATCH_MIN:
             # what a walk leaves over (its last few blocks, or signatures the cache already knew):
             # too few for a device pass, and no counter moves, as for a block checked on the host
-            return [[bool(_core.secp_verify(*it)) for it in res.sig_items()] for res in results]
+            # (CHECKMULTISIG groups are resolved by the kernel's model over the per-entry answers)
+            return [[v == 1 for v in _core.sig_group_resolve_model(
+                [int(_core.secp_verify(*it)) for it in res.sig_items()], res.sig_group_table())] for res in results]
         verify = self.sig_window_verifier
         if verify is None:
             from ..ops import sighash
@@ -1463,6 +1488,7 @@ class ChainState:
             self.sig_stats["host_sighashes"] += res.num_sigs - n_dev
             self.sig_stats["gpu_sighashes_v0"] += res.num_device_v0
             self.sig_stats["gpu_sighashes_partial"] += res.num_device_partial
+            self._count_groups(res)
         self.sig_stats["gpu_batches"] += 1
         self.sig_stats["gpu_sigs"] += total
         self.sig_stats["gpu_windows"] += 1

@@ -569,13 +569,56 @@ void bind_script(py::module_& m) {
        "host model of sig_window_verdicts: per block (n_valid, n_invalid, n_ask_host, first_not_valid) as 4 "
        "little-endian u32, first_not_valid relative to the block (SIG_WINDOW_NONE if every verdict is 1); a verdict "
        "other than 0, 1 or 2 counts as invalid");
+    // ---- CHECKMULTISIG groups (-gpumultisig)
+    m.attr("SIG_GROUP_BYTES") = sizeof(SigGroup);
+    m.attr("SIG_GROUP_MAX_PAIRS") = SIG_GROUP_MAX_PAIRS;
+    auto group_bytes = [](const std::vector<SigGroup>& g) {
+        return py::bytes(reinterpret_cast<const char*>(g.data()), g.size() * sizeof(SigGroup));
+    };
+    auto group_table = [](const py::bytes& table) {
+        const std::string t = table;
+        if (t.size() % sizeof(SigGroup)) throw std::invalid_argument("group table is not a whole number of records");
+        std::vector<SigGroup> g(t.size() / sizeof(SigGroup));
+        if (!t.empty()) std::memcpy(g.data(), t.data(), t.size());
+        return g;
+    };
+    cr.def_property_readonly("sig_groups", [](const ConnectResult& r) {
+        py::list out;
+        for (const SigGroupRec& g : r.sig_groups) out.append(py::make_tuple(g.first, g.n_sigs, g.n_keys));
+        return out;
+    }, "with defer_multisig: (first, n_sigs, n_keys) of every CHECKMULTISIG taken as a group, ascending and disjoint: "
+       "entry first + a * w + d of the deferred signatures is signature a against key a + d, w = n_keys - n_sigs + 1")
+        .def("sig_group_table", [group_bytes](const ConnectResult& r) { return group_bytes(sig_group_table(r)); },
+             "sig_groups as packed SigGroup records (first, n_sigs, n_keys, 0: 4 little-endian u32 each)");
+    m.def("sig_window_groups", [group_bytes](const py::list& results) {
+        std::vector<const ConnectResult*> rs;
+        for (auto r : results) rs.push_back(&r.cast<const ConnectResult&>());
+        return group_bytes(sig_window_groups(rs));
+    }, py::arg("results"),
+       "the group table of consecutive blocks' ConnectResults as one batch: every `first` moved by its block's "
+       "signature base, the prefix sig_window_pack reports as sig_begin");
+    m.def("sig_group_check", [group_table](size_t n_verdicts, const py::bytes& table) {
+        const std::vector<SigGroup> g = group_table(table);
+        sig_group_check(n_verdicts, g.data(), g.size());
+    }, py::arg("n_verdicts"), py::arg("table"),
+       "ValueError on a truncated table, a group with n_sigs = 0, n_sigs > n_keys, n_keys > 20, more than "
+       "SIG_GROUP_MAX_PAIRS pairs or entries past n_verdicts, and on groups that overlap or descend");
+    m.def("sig_group_resolve_model", [group_table](std::vector<u32> verdicts, const py::bytes& table) {
+        const std::vector<SigGroup> g = group_table(table);
+        sig_group_resolve_model(verdicts.data(), verdicts.size(), g.data(), g.size());
+        return verdicts;
+    }, py::arg("verdicts"), py::arg("table"),
+       "host model of sig_group_resolve: CHECKMULTISIG's walk over each group's verdicts (anything but 1 or 2 is a "
+       "failed check), all of the group's entries rewritten to 1 (the walk succeeds), 0 (it fails) or 2 (it read a "
+       "2: the host decides); entries outside groups unchanged. Checks the table first");
     m.def("connect_block", [](const Block& block, int height, CoinsView& view, bool check_scripts, bool defer_sigs,
                               py::object mtp_at, int64_t block_mtp, u32 flags, int threads, assets::State* asset_state,
                               const assets::Flags& asset_flags, const py::bytes& block_hash, bool sigcache,
-                              bool defer_sighash, bool defer_all_forms) {
+                              bool defer_sighash, bool defer_all_forms, bool defer_multisig) {
         ConnectOptions opt;
         opt.defer_sighash = defer_sighash;
         opt.defer_all_forms = defer_all_forms;
+        opt.defer_multisig = defer_multisig;
         opt.assets = asset_state;
         opt.asset_flags = asset_flags;
         const std::string bh = block_hash;
@@ -604,8 +647,11 @@ void bind_script(py::module_& m) {
        py::arg("defer_sigs") = false, py::arg("mtp_at") = py::none(), py::arg("block_mtp") = 0,
        py::arg("flags") = kBlockScriptFlags, py::arg("threads") = 1, py::arg("assets") = nullptr,
        py::arg("asset_flags") = assets::Flags{}, py::arg("block_hash") = py::bytes(), py::arg("sigcache") = true,
-       py::arg("defer_sighash") = false, py::arg("defer_all_forms") = false,
+       py::arg("defer_sighash") = false, py::arg("defer_all_forms") = false, py::arg("defer_multisig") = false,
        "ConnectBlock against the view -> (ConnectResult, serialized CBlockUndo); the view is unchanged on failure. "
+       "defer_multisig (with defer_sigs only): a CHECKMULTISIG whose outcome depends on its pair verdicts alone leaves "
+       "every candidate (signature, key) pair among the deferred signatures and a record in ConnectResult.sig_groups; "
+       "those entries neither consult nor erase the signature cache. "
        "defer_sighash (with defer_sigs only): the legacy SIGHASH_ALL-form message hashes are left to the batch too "
        "(ConnectResult.sighash_pack); those signatures are not looked up in the signature cache, whose key is the "
        "message, so their entries age out of the bounded cache instead of being erased on use. defer_all_forms (with "

@@ -620,6 +620,7 @@ ConnectResult connect_block(const Block& block, int height, CoinsView& view, con
         res.dos = dos;
         res.sigs.clear();
         res.sig_at.clear();
+        res.sig_groups.clear();
         res.templates.clear();
         res.forms.clear();
         return res;
@@ -631,6 +632,7 @@ ConnectResult connect_block(const Block& block, int height, CoinsView& view, con
         bool ok = true;
         ScriptError err = ScriptError::OK;
         std::vector<PendingSig> sigs;
+        std::vector<SigGroupRec> groups;  // `first` relative to sigs
     };
     std::vector<Check> checks;
     std::vector<std::unique_ptr<PrecomputedTx>> caches(block.vtx.size());
@@ -737,6 +739,8 @@ ConnectResult connect_block(const Block& block, int height, CoinsView& view, con
         TxSigChecker checker(&tx, c.i, c.value, all_forms ? &res.forms[c.t]->pre : caches[c.t].get());
         checker.defer_all_forms = all_forms;
         if (opt.defer_sigs) checker.pending = &c.sigs;
+        checker.defer_multisig = opt.defer_sigs && opt.defer_multisig;
+        checker.groups = &c.groups;
         checker.defer_sighash = defer_sighash;
         checker.tx_index = c.t;
         if (opt.sigcache) checker.sigcache = TxSigChecker::CacheMode::USE;
@@ -769,6 +773,10 @@ ConnectResult connect_block(const Block& block, int height, CoinsView& view, con
     for (auto& c : checks) {
         if (!c.ok)
             return fail(std::string("mandatory-script-verify-flag-failed (") + script_error_name(c.err) + ")", 100);
+        for (SigGroupRec g : c.groups) {
+            g.first += u32(res.sigs.size());
+            res.sig_groups.push_back(g);
+        }
         for (auto& p : c.sigs) {
             res.sigs.push_back(std::move(p));
             res.sig_at.emplace_back(c.t, c.i);

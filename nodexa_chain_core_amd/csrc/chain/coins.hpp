@@ -141,6 +141,13 @@ struct ConnectOptions {
     // ANYONECANPAY and witness v0 too; chain/sighash.hpp pack_sighash_var). None of the deferred
     // signatures, witness ones included, is looked up in the signature cache.
     bool defer_all_forms = false;
+    // With defer_sigs: a CHECKMULTISIG whose outcome depends on its pair verdicts alone records
+    // every candidate (signature, key) pair and a group record (interpreter.hpp SigGroupRec), and
+    // the batch runs the pairing walk (chain/sighash.hpp sig_group_resolve_model), so an input
+    // signed by any subset of its keys needs no host re-check. Group entries neither consult nor
+    // erase the signature cache, whatever their hash's origin: like the deferred hashes above,
+    // their cache entries age out instead of being erased on use.
+    bool defer_multisig = false;
     bool sigcache = true;      // skip (and drop) signatures the mempool already verified (sigcache.hpp)
     bool sequence_locks = true;
     // median time past of the block at `height` of this block's chain (BIP68 time locks)
@@ -164,6 +171,8 @@ struct ConnectResult {
     int64_t sigop_cost = 0;
     std::vector<PendingSig> sigs;            // with defer_sigs: every signature to verify
     std::vector<std::pair<u32, u32>> sig_at;  // (tx index, input index) of each entry of sigs
+    // with defer_multisig: the CHECKMULTISIG groups among sigs, ascending and disjoint
+    std::vector<SigGroupRec> sig_groups;
     Bytes asset_undo;                          // the asset journal of the block (with opt.assets)
     // with defer_sighash: the template of every transaction that has a deferred hash, by block index
     std::vector<std::shared_ptr<const SighashTemplate>> templates;

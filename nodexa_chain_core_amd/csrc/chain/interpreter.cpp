@@ -553,28 +553,32 @@ Uint256 signature_hash(const Bytes& script_code, const Transaction& tx, unsigned
     return hash_bytes(w.buf);
 }
 
-bool TxSigChecker::check_sig(const Bytes& sig_in, const Bytes& pubkey, const Bytes& script_code, SigVersion sv) const {
-    // CPubKey(vch).IsValid(): a known header and the matching length
+namespace {
+
+// CPubKey(vch).IsValid(): a known header and the matching length
+bool pubkey_header_ok(const Bytes& pubkey) {
     if (pubkey.empty()) return false;
     const u8 h = pubkey[0];
     const size_t want = (h == 2 || h == 3) ? 33 : (h == 4 || h == 6 || h == 7) ? 65 : 0;
-    if (!want || pubkey.size() != want) return false;
-    if (sig_in.empty()) return false;
-    const int hash_type = sig_in.back();
-    const Bytes sig(sig_in.begin(), sig_in.end() - 1);
+    return want && pubkey.size() == want;
+}
+
+}  // namespace
+
+bool TxSigChecker::deferred_entry(const Bytes& sig, const Bytes& pubkey, const Bytes& script_code, SigVersion sv,
+                                  int hash_type, PendingSig& p) const {
     if (pending && defer_sighash && !defer_all_forms && sighash_all_form(sv, hash_type) && n_in_ < tx_->vin.size()) {
-        PendingSig p{Uint256(), sig, pubkey};
+        p = PendingSig{Uint256(), sig, pubkey};
         p.device_hash = true;
         p.tx_index = tx_index;
         p.n_in = n_in_;
         p.hash_type = hash_type;
         p.code = sighash_script_code(script_code);
-        pending->push_back(std::move(p));
         return true;
     }
     if (pending && defer_sighash && defer_all_forms &&
         sighash_deferrable(tx_->vin.size(), tx_->vout.size(), n_in_, hash_type, sv)) {
-        PendingSig p{Uint256(), sig, pubkey};
+        p = PendingSig{Uint256(), sig, pubkey};
         p.device_hash = true;
         p.tx_index = tx_index;
         p.n_in = n_in_;
@@ -582,6 +586,18 @@ bool TxSigChecker::check_sig(const Bytes& sig_in, const Bytes& pubkey, const Byt
         p.code = sighash_emitted_code(script_code, sv);
         p.sigversion = sv;
         p.amount = amount_;
+        return true;
+    }
+    return false;
+}
+
+bool TxSigChecker::check_sig(const Bytes& sig_in, const Bytes& pubkey, const Bytes& script_code, SigVersion sv) const {
+    if (!pubkey_header_ok(pubkey)) return false;
+    if (sig_in.empty()) return false;
+    const int hash_type = sig_in.back();
+    const Bytes sig(sig_in.begin(), sig_in.end() - 1);
+    PendingSig p;
+    if (deferred_entry(sig, pubkey, script_code, sv, hash_type, p)) {
         pending->push_back(std::move(p));
         return true;
     }
@@ -595,6 +611,38 @@ bool TxSigChecker::check_sig(const Bytes& sig_in, const Bytes& pubkey, const Byt
     const bool ok = secp::verify_der(pubkey.data(), pubkey.size(), sig.data(), sig.size(), msg.data);
     if (ok && sigcache == CacheMode::STORE) SigCache::instance().put(msg.data, pubkey, sig);
     return ok;
+}
+
+bool TxSigChecker::defer_multisig_group(const std::vector<const Bytes*>& sigs, const std::vector<const Bytes*>& keys,
+                                        const Bytes& script_code, SigVersion sv) const {
+    if (!groups_multisig()) return false;
+    const size_t m = sigs.size(), n = keys.size();
+    if (m < 1 || m > n) return false;
+    const size_t w = n - m + 1;
+    if (m * w > kSigGroupMaxPairs) return false;
+    for (const Bytes* k : keys)
+        if (!pubkey_header_ok(*k)) return false;  // check_sig would answer false: the walk decides
+    for (const Bytes* s : sigs)
+        if (s->empty()) return false;
+    const u32 first = u32(pending->size());
+    for (size_t a = 0; a < m; ++a) {
+        const int hash_type = sigs[a]->back();
+        const Bytes sig(sigs[a]->begin(), sigs[a]->end() - 1);
+        bool have_msg = false;
+        Uint256 msg;
+        for (size_t d = 0; d < w; ++d) {
+            const Bytes& pubkey = *keys[a + d];
+            PendingSig p;
+            if (!deferred_entry(sig, pubkey, script_code, sv, hash_type, p)) {
+                if (!have_msg) msg = signature_hash(script_code, *tx_, n_in_, hash_type, amount_, sv, cache_);
+                have_msg = true;
+                p = PendingSig{msg, sig, pubkey};  // the signature cache is not asked: see defer_multisig
+            }
+            pending->push_back(std::move(p));
+        }
+    }
+    groups->push_back(SigGroupRec{first, u32(m), u32(n)});
+    return true;
 }
 
 bool TxSigChecker::check_lock_time(int64_t n) const {
@@ -943,7 +991,28 @@ bool eval_script(std::vector<Bytes>& stack, const Bytes& script, u32 flags, cons
                             if (sv == SigVersion::BASE) find_and_delete(code, push_script(top(-isig - k)));
                         }
                         bool success = true;
-                        while (success && nsigs > 0) {
+                        // A deferring checker answers true to every check_sig, so the walk below would
+                        // pair signature k with key k and try no other key. Where no encoding error can
+                        // arise on any walk, the checker records every candidate pair instead and the
+                        // batch runs this walk over their verdicts; the opcode goes on as a success.
+                        bool grouped = false;
+                        if (nsigs > 0 && checker.groups_multisig()) {
+                            std::vector<const Bytes*> gsigs, gkeys;
+                            ScriptError enc = ScriptError::OK;
+                            bool plain = true;
+                            for (int k = 0; k < nsigs && plain; ++k) {
+                                const Bytes& s = top(-isig - k);
+                                plain = !s.empty() && check_signature_encoding(s, flags, &enc);
+                                gsigs.push_back(&s);
+                            }
+                            for (int k = 0; k < nkeys && plain; ++k) {
+                                const Bytes& pk = top(-ikey - k);
+                                plain = check_pubkey_encoding(pk, flags, sv, &enc);
+                                gkeys.push_back(&pk);
+                            }
+                            grouped = plain && checker.defer_multisig_group(gsigs, gkeys, code, sv);
+                        }
+                        while (!grouped && success && nsigs > 0) {
                             const Bytes& sig = top(-isig);
                             const Bytes& pk = top(-ikey);
                             if (!check_signature_encoding(sig, flags, err) || !check_pubkey_encoding(pk, flags, sv, err))

@@ -162,6 +162,17 @@ public:
     }
     virtual bool check_lock_time(int64_t n) const { (void)n; return false; }
     virtual bool check_sequence(int64_t n) const { (void)n; return false; }
+    // CHECKMULTISIG under a deferring checker (TxSigChecker::defer_multisig). groups_multisig: whether
+    // the checker takes groups at all. defer_multisig_group: record every candidate pair of the
+    // opcode's walk (sigs[0] is the signature on top of the stack, keys[0] the last key of the
+    // script; every signature is non-empty and well encoded, every key passed the encoding rule) and
+    // answer true, or answer false and record nothing: the caller then walks as usual.
+    virtual bool groups_multisig() const { return false; }
+    virtual bool defer_multisig_group(const std::vector<const Bytes*>& sigs, const std::vector<const Bytes*>& keys,
+                                      const Bytes& script_code, SigVersion sv) const {
+        (void)sigs; (void)keys; (void)script_code; (void)sv;
+        return false;
+    }
 };
 
 // A signature check deferred for a batch: message hash, DER signature (hash type stripped) and
@@ -183,6 +194,15 @@ struct PendingSig {
     Amount amount = 0;
 };
 
+// One CHECKMULTISIG taken as a group (defer_multisig): n_sigs signatures against n_keys keys as
+// n_sigs * w consecutive PendingSig entries from `first`, w = n_keys - n_sigs + 1; entry
+// first + a * w + d is signature a against key a + d (a = 0: the signature on top of the stack,
+// key 0: the last key of the script), the only pairs the opcode's walk can reach.
+struct SigGroupRec {
+    u32 first, n_sigs, n_keys;
+};
+constexpr u32 kSigGroupMaxPairs = 64;  // SIG_GROUP_MAX_PAIRS (hip/kernels/kernel_params.h)
+
 class TxSigChecker : public SigChecker {
 public:
     TxSigChecker(const Transaction* tx, unsigned n_in, Amount amount, const PrecomputedTx* cache = nullptr)
@@ -202,6 +222,16 @@ public:
     // the legacy hashes whose message is the constant one (nothing to hash).
     bool defer_all_forms = false;
     u32 tx_index = 0;  // the transaction's index in its block, recorded in deferred hashes
+    // With `pending` and `groups`: a CHECKMULTISIG whose outcome depends on the pair verdicts alone
+    // (no encoding error can arise on any walk, at most kSigGroupMaxPairs pairs) records all its
+    // candidate pairs and one SigGroupRec, and the batch runs the pairing walk over their verdicts
+    // (chain/sighash.hpp sig_group_resolve_model). Group entries neither consult nor erase the
+    // signature cache.
+    bool defer_multisig = false;
+    std::vector<SigGroupRec>* groups = nullptr;
+    bool groups_multisig() const override { return pending && groups && defer_multisig; }
+    bool defer_multisig_group(const std::vector<const Bytes*>& sigs, const std::vector<const Bytes*>& keys,
+                              const Bytes& script_code, SigVersion sv) const override;
     // Signature cache (sigcache.hpp): STORE remembers every signature that verifies (mempool
     // acceptance); USE answers from the cache first and erases what it hits (block validation,
     // CachingTransactionSignatureChecker with store = false).
@@ -209,6 +239,10 @@ public:
     CacheMode sigcache = CacheMode::NONE;
 
 protected:
+    // The entry of a signature whose hash is left to the batch under the flags in force (`sig`
+    // without its hash type); false if the message is computed on the host.
+    bool deferred_entry(const Bytes& sig, const Bytes& pubkey, const Bytes& script_code, SigVersion sv, int hash_type,
+                        PendingSig& p) const;
     const Transaction* tx_;
     unsigned n_in_;
     Amount amount_;

@@ -10,6 +10,30 @@
 
 namespace nodexa {
 
+namespace {
+
+// Whether entry k of res.sigs has the message of entry k - 1, asked for ascending k: both belong to
+// one CHECKMULTISIG group (same input, same script code) and sign with the same hash type, and
+// both hashes are left to the device. Such entries name the same arena ranges.
+class SameMessage {
+public:
+    explicit SameMessage(const ConnectResult& res) : res_(res) {}
+    bool operator()(size_t k) {
+        const std::vector<SigGroupRec>& g = res_.sig_groups;
+        while (gi_ < g.size() && k >= size_t(g[gi_].first) + pairs(g[gi_])) ++gi_;
+        if (gi_ == g.size() || k <= g[gi_].first) return false;
+        const PendingSig &p = res_.sigs[k], &q = res_.sigs[k - 1];
+        return p.device_hash && q.device_hash && p.hash_type == q.hash_type;
+    }
+
+private:
+    static size_t pairs(const SigGroupRec& g) { return size_t(g.n_sigs) * (g.n_keys - g.n_sigs + 1); }
+    const ConnectResult& res_;
+    size_t gi_ = 0;
+};
+
+}  // namespace
+
 SighashPack pack_sighash(const ConnectResult& res) {
     // four fixed segments express the legacy ALL form only
     if (res.all_forms) throw std::invalid_argument("pack_sighash: the block was connected with defer_all_forms");
@@ -17,6 +41,7 @@ SighashPack pack_sighash(const ConnectResult& res) {
     out.secp_jobs.resize(res.sigs.size());
     std::vector<int64_t> tmpl_at(res.templates.size(), -1);  // arena offset of each template placed
     static const u8 kZero[32] = {};
+    SameMessage same_message(res);
     for (size_t k = 0; k < res.sigs.size(); ++k) {
         const PendingSig& p = res.sigs[k];
         SecpVerifyJob& sj = out.secp_jobs[k];
@@ -26,6 +51,15 @@ SighashPack pack_sighash(const ConnectResult& res) {
             continue;
         }
         secp::pack_verify_job(p.pubkey.data(), p.pubkey.size(), p.sig.data(), p.sig.size(), kZero, sj);
+        if (same_message(k)) {  // another key against the message of the entry before: its ranges
+            SighashJob j = out.jobs.back();
+            j.out_index = u32(k);
+            j.kind = sj.kind;
+            sj.kind = SECP_KIND_INVALID;
+            out.jobs.push_back(j);
+            ++out.device_jobs;
+            continue;
+        }
         const SighashTemplate& t = *res.templates.at(p.tx_index);
         if (tmpl_at[p.tx_index] < 0) {
             tmpl_at[p.tx_index] = int64_t(out.arena.size());
@@ -117,6 +151,7 @@ SighashVarPack pack_sighash_var(const ConnectResult& res) {
             put_le32(u32(n));
         }
     };
+    SameMessage same_message(res);
     for (size_t k = 0; k < res.sigs.size(); ++k) {
         const PendingSig& p = res.sigs[k];
         SecpVerifyJob& sj = out.secp_jobs[k];
@@ -128,6 +163,17 @@ SighashVarPack pack_sighash_var(const ConnectResult& res) {
         if (!res.all_forms)
             throw std::invalid_argument("pack_sighash_var: the block was connected without defer_all_forms");
         secp::pack_verify_job(p.pubkey.data(), p.pubkey.size(), p.sig.data(), p.sig.size(), kZero, sj);
+        if (same_message(k)) {  // another key against the message of the entry before: its segments
+            SighashVarJob j = out.jobs.back();
+            j.out_index = u32(k);
+            j.kind = sj.kind;
+            sj.kind = SECP_KIND_INVALID;
+            out.jobs.push_back(j);
+            ++out.device_jobs;
+            if (p.sigversion == SigVersion::WITNESS_V0) ++out.device_v0;
+            else if (!sighash_all_form(SigVersion::BASE, p.hash_type)) ++out.device_partial;
+            continue;
+        }
         const SighashTxForms& f = *res.forms.at(p.tx_index);
         const Bytes& T = f.t.bytes;
         const size_t off = f.t.script_off.at(p.n_in);
@@ -368,6 +414,63 @@ std::vector<SigWindowRecord> sig_window_verdicts_model(const u32* verdicts, size
         out[b] = r;
     }
     return out;
+}
+
+std::vector<SigGroup> sig_group_table(const ConnectResult& res) {
+    std::vector<SigGroup> out;
+    out.reserve(res.sig_groups.size());
+    for (const SigGroupRec& g : res.sig_groups) out.push_back(SigGroup{g.first, g.n_sigs, g.n_keys, 0});
+    return out;
+}
+
+std::vector<SigGroup> sig_window_groups(const std::vector<const ConnectResult*>& results) {
+    std::vector<SigGroup> out;
+    u64 base = 0;
+    for (const ConnectResult* r : results) {
+        if (base + r->sigs.size() >= (u64(1) << 31)) throw std::length_error("signature window: too many signatures");
+        for (const SigGroupRec& g : r->sig_groups) out.push_back(SigGroup{u32(base) + g.first, g.n_sigs, g.n_keys, 0});
+        base += r->sigs.size();
+    }
+    return out;
+}
+
+void sig_group_check(size_t n_verdicts, const SigGroup* groups, size_t ng) {
+    u64 end = 0;  // of the previous group
+    for (size_t k = 0; k < ng; ++k) {
+        const SigGroup& g = groups[k];
+        const std::string who = "signature group " + std::to_string(k);
+        if (g.n_sigs == 0) throw std::invalid_argument(who + ": no signature");
+        if (g.n_sigs > g.n_keys) throw std::invalid_argument(who + ": more signatures than keys");
+        if (g.n_keys > 20) throw std::invalid_argument(who + ": more than 20 keys");
+        const u64 pairs = u64(g.n_sigs) * (g.n_keys - g.n_sigs + 1);
+        if (pairs > SIG_GROUP_MAX_PAIRS) throw std::invalid_argument(who + ": too many pairs");
+        if (g.first < end) throw std::invalid_argument(who + ": overlaps or precedes the group before it");
+        end = u64(g.first) + pairs;
+        if (end > n_verdicts) throw std::invalid_argument(who + ": reaches past the verdicts");
+    }
+}
+
+void sig_group_resolve_model(u32* verdicts, size_t n_verdicts, const SigGroup* groups, size_t ng) {
+    sig_group_check(n_verdicts, groups, ng);
+    for (size_t k = 0; k < ng; ++k) {
+        const u32 m = groups[k].n_sigs, n = groups[k].n_keys, w = n - m + 1;
+        u32* v = verdicts + groups[k].first;
+        u32 a = 0, b = 0, outcome = 1;
+        while (a < m) {
+            const u32 x = v[a * w + (b - a)];
+            if (x == 2) {
+                outcome = 2;
+                break;
+            }
+            if (x == 1) ++a;
+            ++b;
+            if (m - a > n - b) {
+                outcome = 0;
+                break;
+            }
+        }
+        for (u32 i = 0; i < m * w; ++i) v[i] = outcome;
+    }
 }
 
 }  // namespace nodexa

@@ -103,4 +103,28 @@ SigWindowPack pack_sig_window(const std::vector<const ConnectResult*>& results,
 // verdicts. Throws std::invalid_argument on a prefix table that decreases or passes n.
 std::vector<SigWindowRecord> sig_window_verdicts_model(const u32* verdicts, size_t n, const u32* sig_begin, size_t nb);
 
+// ---- CHECKMULTISIG groups (-gpumultisig; hip/kernels/sig_group.hip)
+//
+// connect_block with defer_multisig records every candidate pair of a CHECKMULTISIG as entries of
+// ConnectResult::sigs and one SigGroupRec (interpreter.hpp). The packers above treat those entries
+// like any other; consecutive entries of one group that sign with the same hash type name the same
+// arena ranges (and segments), so the arena grows per group, not per pair.
+//
+// The group table of one result, and of a window (each `first` moved by its block's signature
+// base, the prefix pack_sig_window reports as sig_begin).
+std::vector<SigGroup> sig_group_table(const ConnectResult& res);
+std::vector<SigGroup> sig_window_groups(const std::vector<const ConnectResult*>& results);
+// Throws std::invalid_argument on a group with n_sigs = 0, n_sigs > n_keys, n_keys > 20, more than
+// SIG_GROUP_MAX_PAIRS pairs or entries past n_verdicts, and on groups that overlap or descend.
+void sig_group_check(size_t n_verdicts, const SigGroup* groups, size_t ng);
+// The definition of sig_group_resolve, in place. Per group, m = n_sigs, n = n_keys, w = n - m + 1:
+//   a = b = 0
+//   while a < m:  v = verdicts[first + a * w + (b - a)]
+//                 v == 2: ASK, stop;  v == 1: a += 1;  b += 1;  m - a > n - b: FAIL, stop
+//   else OK
+// which is CHECKMULTISIG's own loop (a verdict other than 1 or 2 is a failed check); the entries
+// the walk never reads do not matter. All m * w entries become 1 (OK), 0 (FAIL) or 2 (ASK: the
+// host decides); entries outside groups are untouched. Checks the table first.
+void sig_group_resolve_model(u32* verdicts, size_t n_verdicts, const SigGroup* groups, size_t ng);
+
 }  // namespace nodexa

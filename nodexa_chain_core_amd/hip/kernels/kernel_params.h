@@ -404,3 +404,21 @@ struct HeaderBatchParams {
     uint8_t pow_limit[32];     // consensus powLimit, little-endian (CheckProofOfWork's target cap)
 };
 
+// CHECKMULTISIG pairings over the verifier's verdicts (sig_group.hip sig_group_resolve). A group is
+// one CHECKMULTISIG of n_sigs signatures and n_keys keys whose candidate pairs were all verified:
+// n_sigs * w consecutive verdicts from `first`, w = n_keys - n_sigs + 1, entry first + a * w + d
+// being signature a against key a + d (both in the interpreter's walk order). The kernel runs the
+// walk and rewrites all of the group's entries to its outcome: 1 the walk succeeds, 0 it fails,
+// 2 it read a verdict 2 (the host decides). csrc/chain/sighash.hpp sig_group_check states what a
+// table must satisfy before it reaches the device.
+#define SIG_GROUP_MAX_PAIRS 64u
+struct SigGroup {
+    uint32_t first, n_sigs, n_keys, pad;
+};
+struct SigGroupParams {
+    uint32_t* verdicts;              // secp_verify_batch's out[], rewritten in place
+    const struct SigGroup* groups;   // ng records, ascending and disjoint
+    uint32_t ng;
+    uint32_t pad;
+};
+

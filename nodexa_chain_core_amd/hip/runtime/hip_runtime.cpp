@@ -677,6 +677,22 @@ PYBIND11_MODULE(_hip, m) {
         k.launch_bytes(dim3((nb + 3) / 4), dim3(256), 0, as_stream(stream), &p, sizeof(p));
     });
 
+    // ---- CHECKMULTISIG pairings over the verifier's verdicts (sig_group.hip): one lane per group. The
+    // caller has checked the table against the verdict count (_core.sig_group_check); the table is
+    // 16-byte aligned. ng = 0 launches nothing.
+    m.attr("SIG_GROUP_BYTES") = sizeof(SigGroup);
+    m.def("launch_sig_group_resolve", [](const Kernel& k, uintptr_t verdicts, uintptr_t groups, uint32_t ng,
+                                         uintptr_t stream) {
+        if (ng == 0) return;
+        if (!verdicts || !groups) throw std::invalid_argument("sig_group: null table");
+        if (groups % 16) throw std::invalid_argument("sig_group: group table not 16-byte aligned");
+        SigGroupParams p{};
+        p.verdicts = reinterpret_cast<uint32_t*>(verdicts);
+        p.groups = reinterpret_cast<const SigGroup*>(groups);
+        p.ng = ng;
+        k.launch_bytes(dim3((ng + 255) / 256), dim3(256), 0, as_stream(stream), &p, sizeof(p));
+    });
+
     // ---- Equihash(200,9): one full Wagner solve for `num_inst` inputs, enqueued on `stream`
     m.attr("EQ_BUCKETS") = EQ_BUCKETS;
     m.attr("EQ_WORDS") = EQ_WORDS;

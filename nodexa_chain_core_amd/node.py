@@ -327,6 +327,10 @@ class Node:
         # -gpusigwindow=<signatures>: with the GPU batch, verify the signatures of consecutive stored
         # blocks (sync, reindex, a long reorg) in one device pass of about this many; 0 = block by block
         self.state.gpu_sig_window = max(0, a.get_int("gpusigwindow", 0))
+        # -gpumultisig=0|1: with the GPU batch, verify every candidate (signature, key) pair of a
+        # CHECKMULTISIG in the batch and resolve the pairing on the GPU, so that a multisig input signed
+        # by any subset of its keys needs no host re-check; 0 = signature k against key k only
+        self.state.gpu_multisig = 1 if a.get_int("gpumultisig", 0) > 0 else 0
         if self.datadir is not None:  # fee_estimates.dat (src/init.cpp: est_filein), before the mempool
             self.state.load_fee_estimates(os.path.join(self.datadir, "fee_estimates.dat"))
         if self.datadir is not None and a.get_bool("persistmempool", True):  # -persistmempool (LoadMempool)

@@ -31,9 +31,15 @@ def _gen_table(dev: torch.device) -> torch.Tensor:
         return t
 
 
-def verify_batch_raw(items: list[tuple[bytes, bytes, bytes]], device: int | None = None) -> list[int]:
+def verify_batch_raw(items: list[tuple[bytes, bytes, bytes]], device: int | None = None,
+                     groups: bytes | None = None) -> list[int]:
     """The kernel's own verdict for each item of `verify_batch`: 1 valid, 0 invalid, 2 "an addition
-    met a doubling / inverse case, ask the host". Nothing is re-checked here."""
+    met a doubling / inverse case, ask the host". Nothing is re-checked here. With `groups` (a
+    packed SigGroup table, `ConnectResult.sig_group_table()`), `sig_group_resolve` follows the
+    verifier on the same stream and every entry of a group carries the outcome of its
+    CHECKMULTISIG's walk instead."""
+    if groups:
+        _core.sig_group_check(len(items), groups)  # nothing malformed reaches the device
     if not items:
         return []
     runtime.require_gpu()
@@ -46,15 +52,24 @@ def verify_batch_raw(items: list[tuple[bytes, bytes, bytes]], device: int | None
         out = torch.empty(len(items), dtype=torch.int32, device=dev)
         h.launch_secp_verify(kern, jobs.data_ptr(), len(items), _gen_table(dev).data_ptr(), out.data_ptr(),
                              runtime.current_stream_handle())
+        if groups:
+            d_groups = torch.frombuffer(bytearray(groups), dtype=torch.int32).to(dev)
+            h.launch_sig_group_resolve(runtime.static_kernel("sig_group", "sig_group_resolve"), out.data_ptr(),
+                                       d_groups.data_ptr(), len(groups) // _core.SIG_GROUP_BYTES,
+                                       runtime.current_stream_handle())
         return out.cpu().tolist()
 
 
 @traced("secp.verify_batch")
-def verify_batch(items: list[tuple[bytes, bytes, bytes]], device: int | None = None) -> list[bool]:
+def verify_batch(items: list[tuple[bytes, bytes, bytes]], device: int | None = None,
+                 groups: bytes | None = None) -> list[bool]:
     """items: (public key, DER signature without the hash-type byte, 32-byte message).
-    Returns CPubKey::Verify's answer for each (lax DER, high S accepted)."""
+    Returns CPubKey::Verify's answer for each (lax DER, high S accepted). With `groups` (the packed
+    table of a `connect_block(defer_multisig=True)` result) an entry is True if its signature is
+    valid, or if its group's CHECKMULTISIG walk succeeded; an entry of a group whose walk failed is
+    False, and one whose walk met a verdict 2 gets its own host answer."""
     res = []
-    for (pub, sig, msg), v in zip(items, verify_batch_raw(items, device)):
+    for (pub, sig, msg), v in zip(items, verify_batch_raw(items, device, groups)):
         if v == 2:  # a doubling / inverse case inside an addition: the host decides
             res.append(bool(_core.secp_verify(pub, sig, msg)))
         else:

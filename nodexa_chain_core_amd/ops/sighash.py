@@ -24,6 +24,13 @@ kernel on its own, and `verify_block_sigs` takes this path for such a result.
 all of them, and `sig_window_verdicts` (hip/kernels/sig_window.hip) condenses the verdicts to one
 16-byte record per block, the only thing that comes back while every signature is valid.
 `verdict_records` is that kernel on its own.
+
+A result connected with `defer_multisig=True` carries CHECKMULTISIG groups (`res.sig_groups`): all
+candidate (signature, key) pairs of the opcode's walk are entries of the batch.
+`sig_group_resolve` (hip/kernels/sig_group.hip) runs between the verifier and
+`sig_window_verdicts`, on the same stream, and rewrites each group's verdicts to the outcome of
+its walk, so an entry is True if its signature is valid, or if its group's walk succeeded.
+`resolve_groups` is that kernel on its own.
 """
 from __future__ import annotations
 
@@ -141,13 +148,43 @@ def gather_var_into_secp(arena: bytes, segs: bytes, jobs: bytes, secp_jobs: byte
         return d_secp.cpu().numpy().tobytes()
 
 
+GROUP_BYTES = _core.SIG_GROUP_BYTES
+
+
+def _launch_groups(h, d_out: torch.Tensor, n: int, table: bytes, dev: torch.device, stream) -> None:
+    """sig_group_resolve over the verifier's out[] in place; nothing malformed reaches the device."""
+    _core.sig_group_check(n, table)
+    if not table:
+        return
+    d_groups = torch.frombuffer(bytearray(table), dtype=torch.int32).to(dev)
+    h.launch_sig_group_resolve(runtime.static_kernel("sig_group", "sig_group_resolve"), d_out.data_ptr(),
+                               d_groups.data_ptr(), len(table) // GROUP_BYTES, stream)
+
+
+def resolve_groups(verdicts, table: bytes, device: int | None = None) -> list[int]:
+    """`sig_group_resolve` on its own: the verdict array with every group's entries rewritten to the
+    outcome of its CHECKMULTISIG walk. Equals `_core.sig_group_resolve_model(verdicts, table)`."""
+    v = np.asarray(verdicts, dtype=np.uint32)
+    _core.sig_group_check(len(v), table)
+    if not table:
+        return [int(x) for x in v]
+    runtime.require_gpu()
+    dev = _device(device)
+    with torch.cuda.device(dev):
+        d_out = torch.from_numpy(v.view(np.int32).copy()).to(dev)
+        _launch_groups(runtime.hip(), d_out, len(v), table, dev, runtime.current_stream_handle())
+        return [int(x) for x in d_out.cpu().numpy().view(np.uint32)]
+
+
 @traced("sighash.verify_block_sigs")
 def verify_block_sigs(res, device: int | None = None) -> list[bool]:
     """CPubKey::Verify's answer for every deferred signature of a `connect_block(defer_sigs=True,
     defer_sighash=True)` result (with or without `defer_all_forms`), in the order of
     `res.sig_items()`. The message hashes left to the
     batch are computed on the device and never come back; only the verdicts do. A verdict 2
-    (degenerate addition) is re-checked on the host with the host-computed message."""
+    (degenerate addition) is re-checked on the host with the host-computed message. With
+    `defer_multisig` groups in the result, an entry is True if its signature is valid, or if its
+    group's CHECKMULTISIG walk succeeded."""
     n = res.num_sigs
     if n == 0:
         return []
@@ -175,6 +212,7 @@ def verify_block_sigs(res, device: int | None = None) -> list[bool]:
                                     d_jobs.data_ptr(), n_dev, 0, d_secp.data_ptr(), stream)
         h.launch_secp_verify(runtime.static_kernel("secp256k1_verify", "secp_verify_batch"), d_secp.data_ptr(), n,
                              gtab.data_ptr(), out.data_ptr(), stream)
+        _launch_groups(h, out, n, res.sig_group_table(), dev, stream)
         verdicts = out.cpu().tolist()
     if 2 in verdicts:
         items = res.sig_items()
@@ -222,8 +260,9 @@ def verdict_records(verdicts, sig_begin, device: int | None = None) -> bytes:
 
 def _window_pass(results, device: int | None):
     """One pack, one upload of each table, gather (if any hash is left to the device),
-    secp_verify_batch, sig_window_verdicts: -> (records (nb, 4) uint32, verdicts on the device,
-    sig_begin), or None for a window without signatures, which launches nothing."""
+    secp_verify_batch, sig_group_resolve (if any result carries groups), sig_window_verdicts: ->
+    (records (nb, 4) uint32, verdicts on the device, sig_begin), or None for a window without
+    signatures, which launches nothing."""
     mode, arena, segs, jobs, secp_jobs, sig_begin, n_dev, _n_host = _core.sig_window_pack(list(results))
     n = sig_begin[-1]
     if n == 0:
@@ -248,6 +287,7 @@ def _window_pass(results, device: int | None):
                                     d_jobs.data_ptr(), n_dev, 0, d_secp.data_ptr(), stream)
         h.launch_secp_verify(runtime.static_kernel("secp256k1_verify", "secp_verify_batch"), d_secp.data_ptr(), n,
                              gtab.data_ptr(), out.data_ptr(), stream)
+        _launch_groups(h, out, n, _core.sig_window_groups(list(results)), dev, stream)
         records = _launch_records(h, out, sb, dev, stream).cpu().numpy().view(np.uint32)
     return records, out, sb
 
@@ -269,7 +309,8 @@ def verify_window(results, device: int | None = None) -> list[list[bool]]:
     `verify_block_sigs(results[b])` (or `secp.verify_batch(results[b].sig_items())` for a result
     whose hashes came from the host) returns. All results are of one -gpusighash mode. Only one
     16-byte record per block comes back; the verdicts of a block are fetched when its record shows
-    one that is not valid, and a verdict 2 is re-checked on the host with the host-computed message."""
+    one that is not valid, and a verdict 2 is re-checked on the host with the host-computed message.
+    Groups (`defer_multisig`) are resolved on the device before the records are made."""
     got = _window_pass(results, device)
     if got is None:
         return [[] for _ in results]

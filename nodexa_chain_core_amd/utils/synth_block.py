@@ -32,8 +32,14 @@ def _coinbase(height: int):
     return cb
 
 
+def _multisig_key(seed: int, gi: int, k: int) -> bytes:
+    # the first three keys of an input are the ones its 2-of-3 has always had
+    return _key(seed, 3 * gi + k) if k < 3 else _key(seed, (1 << 24) + 32 * gi + k)
+
+
 def make_consolidation_block(n_txs: int, inputs_per_tx, seed: int = 0, hash_types=(1,), witness_every: int = 0,
-                             multisig_every: int = 0, bad_at: int | None = None, height: int = 1000):
+                             multisig_every: int = 0, bad_at: int | None = None, height: int = 1000,
+                             multisig_mn=(2, 3), multisig_signers=None, multisig_kind: str = "p2sh"):
     """-> (block, view, height, info): `n_txs` transactions that each spend many seeded coins into
     two outputs, the shape whose legacy signature hashes cost the host quadratic work.
 
@@ -42,10 +48,30 @@ def make_consolidation_block(n_txs: int, inputs_per_tx, seed: int = 0, hash_type
     transaction); input g signs with hash_types[g % len(hash_types)], is P2WPKH when
     `witness_every` divides g + 1, else P2SH 2-of-3 when `multisig_every` divides g + 1 (two
     signatures), else P2PKH. With `bad_at`, the first signature of that input is corrupted.
+    The multisig inputs are m-of-n for `multisig_mn` = (m, n), paid to a script hash ("p2sh"), to the
+    bare script ("bare") or to a witness script hash ("p2wsh") as `multisig_kind` says.
+    `multisig_signers` names the keys that sign, by their index in the script: None for the last m,
+    a tuple of m indices for the same keys in every input, or "cycle" for every m-subset in turn, one
+    per multisig input. Signatures are pushed in key order, as CHECKMULTISIG demands.
     `info` counts what the block implies: "inputs", "sigs", "device_sigs" (legacy signatures whose
     hash has the SIGHASH_ALL form: no ANYONECANPAY, base type neither NONE nor SINGLE),
-    "host_sigs" (the rest), and "bad_sig" (index of the corrupted signature among "sigs")."""
+    "host_sigs" (the rest), and "bad_sig" (index of the corrupted signature among "sigs", where
+    CHECKMULTISIG's walk meets every signature's key at the first try: the last m keys signing)."""
+    import itertools
     import random
+
+    ms_m, ms_n = multisig_mn
+    if multisig_kind not in ("p2sh", "bare", "p2wsh"):
+        raise ValueError("multisig_kind: p2sh, bare or p2wsh")
+    if multisig_signers is None:
+        subsets = [tuple(range(ms_n - ms_m, ms_n))]
+    elif multisig_signers == "cycle":
+        subsets = list(itertools.combinations(range(ms_n), ms_m))
+    else:
+        subsets = [tuple(sorted(multisig_signers))]
+        if len(set(subsets[0])) != ms_m or not all(0 <= j < ms_n for j in subsets[0]):
+            raise ValueError("multisig_signers: m distinct key indices below n")
+    n_multisig = 0
 
     rng = random.Random(seed)
     view = _core.CoinsView()
@@ -59,11 +85,21 @@ def make_consolidation_block(n_txs: int, inputs_per_tx, seed: int = 0, hash_type
             gi = g + i
             witness = witness_every > 0 and (gi + 1) % witness_every == 0
             multisig = not witness and multisig_every > 0 and (gi + 1) % multisig_every == 0
-            secs = [_key(seed, 3 * gi + k) for k in range(3 if multisig else 1)]
+            secs = [_multisig_key(seed, gi, k) for k in range(ms_n)] if multisig else [_key(seed, 3 * gi)]
             pubs = [_core.secp_pubkey_create(s, True) for s in secs]
             if multisig:
-                redeem = b"\x52" + b"".join(_core.script_push_data(p) for p in pubs) + b"\x53\xae"
-                spk, code = b"\xa9\x14" + _core.hash160(redeem) + b"\x87", redeem
+                redeem = _core.script_push_int(ms_m) + b"".join(_core.script_push_data(p) for p in pubs) + \
+                    _core.script_push_int(ms_n) + b"\xae"
+                code = redeem
+                if multisig_kind == "p2sh":
+                    spk = b"\xa9\x14" + _core.hash160(redeem) + b"\x87"
+                elif multisig_kind == "bare":
+                    spk = redeem
+                else:
+                    spk = b"\x00\x20" + hashlib.sha256(redeem).digest()
+                    witness = True  # signs the BIP143 hash
+                secs = [secs[j] for j in subsets[n_multisig % len(subsets)]]
+                n_multisig += 1
             else:
                 redeem = None
                 code = b"\x76\xa9\x14" + _core.hash160(pubs[0]) + b"\x88\xac"
@@ -88,26 +124,30 @@ def make_consolidation_block(n_txs: int, inputs_per_tx, seed: int = 0, hash_type
         for i, (witness, redeem, code, secs, pubs, value, ht) in enumerate(spends):
             msg = _core.signature_hash(code, raw, i, ht, value, 1 if witness else 0)
             sigs = []
-            # 2-of-3: the last two keys sign, so that CHECKMULTISIG's walk (last signature against
-            # last key first) pairs every signature with its key at the first try, as a deferring
-            # checker assumes
-            for k, sec in enumerate(secs[-2:]):
+            # m-of-n: by default the last m keys sign, so that CHECKMULTISIG's walk (last signature
+            # against last key first) meets every signature's key at the first try. A deferring
+            # checker without defer_multisig tries no other key: any other choice of signers
+            # (multisig_signers) sends the input to the host re-check there
+            for k, sec in enumerate(secs):
                 sig = bytearray(_core.secp_sign(msg, sec))
                 if bad_at == g + i and k == 0:
                     sig[-3] ^= 0x01  # inside S: still valid DER, wrong signature
                     # position in connect_block's deferred order, where a multisig input's
                     # signatures come last first
-                    info["bad_sig"] = info["sigs"] + (1 if redeem is not None else 0)
+                    info["bad_sig"] = info["sigs"] + (len(secs) - 1 if redeem is not None else 0)
                 sigs.append(bytes(sig) + bytes([ht & 0xff]))
                 info["sigs"] += 1
                 legacy_all = not witness and not (ht & 0x80) and (ht & 0x1f) not in (2, 3)
                 info["device_sigs" if legacy_all else "host_sigs"] += 1
-            if witness:
+            if witness and redeem is not None:
+                vins[i].witness = [b""] + sigs + [redeem]
+                vins[i].script_sig = b""
+            elif witness:
                 vins[i].witness = [sigs[0], pubs[0]]
                 vins[i].script_sig = b""
             elif redeem is not None:
                 vins[i].script_sig = b"\x00" + b"".join(_core.script_push_data(s) for s in sigs) + \
-                    _core.script_push_data(redeem)
+                    (_core.script_push_data(redeem) if multisig_kind == "p2sh" else b"")
             else:
                 vins[i].script_sig = _core.script_push_data(sigs[0]) + _core.script_push_data(pubs[0])
         tx.vin = vins
