@@ -35,8 +35,7 @@
 //     for between two hashes (profiles/README r11).
 //   * each round's 256-byte DAG item is one coalesced 16 B/lane load by the
 //     group (lane l takes words ((l^r)%16)*4..+3).
-#include "kernel_params.h"
-#include "keccak_device.hpp"
+#include "kawpow_device.hpp"
 
 // Ceiling microbenchmark (tools/kawpow_sweep.py, profiles/r4a): compile one class of the period's
 // ops out of the real kernel at the shipping occupancy. KP_SKEL_NOMATH keeps the DAG gather chain
@@ -49,7 +48,7 @@
 #define KP_CACHE_OP(...)
 #endif
 #ifndef KAWPOW_PROGRAM_HEADER
-#define KAWPOW_PROGRAM_HEADER "kawpow_program_default.inc"
+#error "KAWPOW_PROGRAM_HEADER is not set: ops/jit.py compile_period writes the period's program (csrc/pow/kawpow_codegen.cpp) to a file and passes its path in this define"
 #endif
 #include KAWPOW_PROGRAM_HEADER
 
@@ -127,18 +126,11 @@ NX_DEV uint4 kp_dag_load(const uint4* p) {
 // (profiles/README r2b).
 NX_DEV uint32_t kp_mul33(uint32_t a) { return a * 33u; }
 
-NX_DEV uint32_t kp_clz(uint32_t x) { return x ? (uint32_t)__builtin_clz(x) : 32u; }
-NX_DEV uint32_t kp_fnv1a(uint32_t h, uint32_t d) { return (h ^ d) * 0x01000193u; }
 NX_DEV uint32_t kp_fastmod(uint32_t x, const FastMod32& f) {
 #if defined(KP_BARRETT)
-    // q' = floor(x * floor(2^32/d) / 2^32) is q or q-1, so r' < 2d and one
-    // unsigned min(r', r'-d) finishes it (r'-d wraps high when r' < d).
-    const uint32_t r = x - __umulhi(x, f.mb) * f.d;
-    return min(r, r - f.d);
+    return kp_mod(x, f);
 #else
-    const uint32_t t = __umulhi(x, f.m);
-    const uint32_t q = (t + ((x - t) >> 1)) >> (f.s - 1);
-    return x - q * f.d;
+    return kp_mod_shift(x, f);
 #endif
 }
 
@@ -222,63 +214,6 @@ NX_DEV uint32_t kp_bcast(uint32_t x) {
     return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0x150 + J, 0xf, 0xf, false);
 }
 
-struct KpKiss {
-    uint32_t z, w, jsr, jcong;
-    NX_DEV uint32_t next() {
-        z = 36969u * (z & 0xffffu) + (z >> 16);
-        w = 18000u * (w & 0xffffu) + (w >> 16);
-        jcong = 69069u * jcong + 1234567u;
-        jsr ^= (jsr << 17);
-        jsr ^= (jsr >> 13);
-        jsr ^= (jsr << 5);
-        return (((z << 16) + w) ^ jcong) + jsr;
-    }
-};
-
-// "rAVENCOINKAWPOW" padding words (one byte per u32).
-#define KP_PAD0 0x72u
-#define KP_PAD1 0x41u
-#define KP_PAD2 0x56u
-#define KP_PAD3 0x45u
-#define KP_PAD4 0x4Eu
-#define KP_PAD5 0x43u
-#define KP_PAD6 0x4Fu
-#define KP_PAD7 0x49u
-#define KP_PAD8 0x4Eu
-#define KP_PAD9 0x4Bu
-#define KP_PAD10 0x41u
-#define KP_PAD11 0x57u
-#define KP_PAD12 0x50u
-#define KP_PAD13 0x4Fu
-#define KP_PAD14 0x57u
-
-NX_DEV void kp_seed(const uint32_t header[8], uint64_t nonce, uint32_t st2[8]) {
-    uint32_t s[25];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) s[i] = header[i];
-    s[8] = (uint32_t)nonce;
-    s[9] = (uint32_t)(nonce >> 32);
-    s[10] = KP_PAD0; s[11] = KP_PAD1; s[12] = KP_PAD2; s[13] = KP_PAD3; s[14] = KP_PAD4;
-    s[15] = KP_PAD5; s[16] = KP_PAD6; s[17] = KP_PAD7; s[18] = KP_PAD8; s[19] = KP_PAD9;
-    s[20] = KP_PAD10; s[21] = KP_PAD11; s[22] = KP_PAD12; s[23] = KP_PAD13; s[24] = KP_PAD14;
-    keccak_f800(s);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) st2[i] = s[i];
-}
-
-NX_DEV void kp_final(const uint32_t st2[8], const uint32_t digest[8], uint32_t out[8]) {
-    uint32_t s[25];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) s[i] = st2[i];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) s[8 + i] = digest[i];
-    s[16] = KP_PAD0; s[17] = KP_PAD1; s[18] = KP_PAD2; s[19] = KP_PAD3; s[20] = KP_PAD4;
-    s[21] = KP_PAD5; s[22] = KP_PAD6; s[23] = KP_PAD7; s[24] = KP_PAD8;
-    keccak_f800(s);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) out[i] = s[i];
-}
-
 // The group's 16 hashes, KP_HASHES at a time. `st0/st1` are this thread's own
 // nonce seed words (hash h's seed lives in lane h). Each finished hash's 8
 // digest words go to `own` of the lane that owns the hash (8 DPP broadcasts).
@@ -320,10 +255,7 @@ NX_DEV void kp_group_hashes(const KP_DAG& dag, const FastMod32& items, const uin
         for (int k = 0; k < KP_HASHES; ++k) {
             const uint32_t s0 = SEEDS_IN_LDS ? seeds[h0 + k] : __shfl(st0, (int)(h0 + k), 16);
             const uint32_t s1 = SEEDS_IN_LDS ? seeds[KP_BLOCK + h0 + k] : __shfl(st1, (int)(h0 + k), 16);
-            const uint32_t z = kp_fnv1a(0x811c9dc5u, s0);
-            const uint32_t w = kp_fnv1a(z, s1);
-            const uint32_t jsr = kp_fnv1a(w, lane);
-            KpKiss rng{z, w, jsr, kp_fnv1a(jsr, lane)};
+            KpKiss rng = kp_mix_rng(s0, s1, lane);
 #pragma unroll
             for (int i = 0; i < 32; ++i) mx[k][i] = rng.next();
         }
@@ -341,13 +273,13 @@ NX_DEV void kp_group_hashes(const KP_DAG& dag, const FastMod32& items, const uin
         }
 #pragma unroll
         for (int k = 0; k < KP_HASHES; ++k) {
-            uint32_t lh = 0x811c9dc5u;
+            uint32_t lh = KP_FNV_OFFSET;
 #pragma unroll
             for (int i = 0; i < 32; ++i) lh = kp_fnv1a(lh, mx[k][i]);
-            // digest[j] = fnv1a(fnv1a(basis, lane_hash[j]), lane_hash[j + 8]); lanes 0..7 own j
+            // digest[j] = fold(lane_hash[j], lane_hash[j + 8]); lanes 0..7 own j
             const uint32_t hi = __shfl(lh, (int)(lane + 8), 16);
             // lanes 0..7 hold the digest words; lane h0+k keeps all 8 of them
-            const uint32_t word = kp_fnv1a(kp_fnv1a(0x811c9dc5u, lh), hi);
+            const uint32_t word = kp_digest_fold(lh, hi);
             const bool mine = lane == h0 + (uint32_t)k;
             // every lane runs the (convergent) broadcasts; only the owner keeps them
             const uint32_t b0 = kp_bcast<0>(word), b1 = kp_bcast<1>(word), b2 = kp_bcast<2>(word),
@@ -375,14 +307,7 @@ extern "C" __global__ KP_BOUNDS void kawpow_search(KawpowSearchParams p) {
     __shared__ uint32_t park[KP_PARK][KP_BLOCK];
     uint32_t* stale = &stale_word;
     if (blockDim.x != KP_BLOCK) return;  // launched with the wrong block: no shares rather than bad ones
-    if (threadIdx.x == 0) {
-        // one uncached read of the host-mapped generation word per workgroup, overlapped with the
-        // L1 fill below: a template change stops queued work within one workgroup's lifetime
-        uint32_t s = 0;
-        if (p.gen_word) s = __hip_atomic_load(p.gen_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != p.generation;
-        *stale = s;
-        if (s) atomicAdd(&p.results->skipped, 1u);
-    }
+    if (threadIdx.x == 0) kp_check_stale(stale, p.gen_word, p.generation, p.results);
     kp_fill_l1(l1, p.dag);
     __syncthreads();
     const uint32_t is_stale = *stale;
@@ -408,19 +333,7 @@ extern "C" __global__ KP_BOUNDS void kawpow_search(KawpowSearchParams p) {
 #pragma unroll
     for (int k = 0; k < KP_PARK; ++k) st2[k] = park[k][threadIdx.x];
     kp_final(st2, digest, fin);
-    const uint64_t head = ((uint64_t)__builtin_bswap32(fin[0]) << 32) | __builtin_bswap32(fin[1]);
-    if (head <= p.target) {
-        const uint32_t slot = atomicAdd(&p.results->count, 1u);
-        if (slot < NODEXA_KAWPOW_MAX_SHARES) {
-            KawpowShare* s = &p.results->shares[slot];
-            s->nonce = nonce;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                s->mix[k] = digest[k];
-                s->final_[k] = fin[k];
-            }
-        }
-    }
+    kp_append_share(p.results, p.target, nonce, digest, fin);
 }
 
 // Batch hash (no target): for verification of (header, nonce, height) jobs that
@@ -439,6 +352,8 @@ extern "C" __global__ KP_BOUNDS void kawpow_hash_batch(KawpowHashParams p) {
     kp_group_hashes(KP_DAG_HANDLE(p.dag), p.items, l1, st2[0], st2[1], lane, digest);
     kp_final(st2, digest, fin);
     if (valid) {
+        // kp_store_hash's row, kept inline: through the call the register allocation of this
+        // kernel's seed keccak moves, and this file's code is held instruction for instruction
         uint32_t* o = p.out + (size_t)job * 16;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {

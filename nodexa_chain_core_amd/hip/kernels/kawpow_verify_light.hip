@@ -25,44 +25,10 @@
 //     staged per group in LDS, so jobs of any period share a launch; the
 //     32-word mix of each lane lives in LDS ([group][reg][lane], conflict-free
 //     for a group's uniform register index).
-#include "kernel_params.h"
-#include "keccak_device.hpp"
+#include "kawpow_device.hpp"
 
 #define KL_BLOCK 256
 #define KL_GROUPS (KL_BLOCK / 16)
-
-NX_DEV uint32_t kl_fnv1(uint32_t u, uint32_t v) { return (u * 0x01000193u) ^ v; }
-NX_DEV uint32_t kl_fnv1a(uint32_t h, uint32_t d) { return (h ^ d) * 0x01000193u; }
-NX_DEV uint32_t kl_mod(uint32_t x, const FastMod32& f) {
-    const uint32_t r = x - __umulhi(x, f.mb) * f.d;  // Barrett estimate, one correction (kernel_params.h)
-    return min(r, r - f.d);
-}
-NX_DEV uint32_t kl_clz(uint32_t x) { return x ? (uint32_t)__builtin_clz(x) : 32u; }
-
-NX_DEV uint32_t kl_merge(uint32_t a, uint32_t b, uint32_t kind, uint32_t rot) {
-    switch (kind) {
-        case 0: return a * 33u + b;
-        case 1: return (a ^ b) * 33u;
-        case 2: return __builtin_rotateleft32(a, rot) ^ b;
-        default: return __builtin_rotateright32(a, rot) ^ b;
-    }
-}
-
-NX_DEV uint32_t kl_math(uint32_t a, uint32_t b, uint32_t kind) {
-    switch (kind) {
-        case 0: return a + b;
-        case 1: return a * b;
-        case 2: return __umulhi(a, b);
-        case 3: return min(a, b);
-        case 4: return __builtin_rotateleft32(a, b);
-        case 5: return __builtin_rotateright32(a, b);
-        case 6: return a & b;
-        case 7: return a | b;
-        case 8: return a ^ b;
-        case 9: return kl_clz(a) + kl_clz(b);
-        default: return (uint32_t)(__builtin_popcount(a) + __builtin_popcount(b));
-    }
-}
 
 // Broadcast the value of lane C of each aligned quad (DPP quad_perm).
 template <int C>
@@ -76,7 +42,7 @@ NX_DEV uint4 kl_item512(const uint4* __restrict__ light, const FastMod32& lmod, 
     uint32_t m[4];
     {
         // every quad lane runs the 64-byte keccak512 seed itself (cheap next to 512 parents)
-        const uint32_t li = kl_mod(index, lmod);
+        const uint32_t li = kp_mod(index, lmod);
         uint64_t in[8], out[8];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -106,12 +72,12 @@ NX_DEV uint4 kl_item512(const uint4* __restrict__ light, const FastMod32& lmod, 
                 case 2: mk = kl_quad_bcast<2>(own); break;
                 default: mk = kl_quad_bcast<3>(own); break;
             }
-            const uint32_t parent = kl_mod(kl_fnv1(index ^ (j + (uint32_t)k), mk), lmod);
+            const uint32_t parent = kp_mod(kp_fnv1(index ^ (j + (uint32_t)k), mk), lmod);
             const uint4 v = light[(size_t)parent * 4 + s];
-            m[0] = kl_fnv1(m[0], v.x);
-            m[1] = kl_fnv1(m[1], v.y);
-            m[2] = kl_fnv1(m[2], v.z);
-            m[3] = kl_fnv1(m[3], v.w);
+            m[0] = kp_fnv1(m[0], v.x);
+            m[1] = kp_fnv1(m[1], v.y);
+            m[2] = kp_fnv1(m[2], v.z);
+            m[3] = kp_fnv1(m[3], v.w);
         }
     }
     // final keccak512 over the whole 16-word mix: gather it from the quad
@@ -162,37 +128,14 @@ NX_DEV void kl_verify(const KawpowLightParams& p) {
     const uint4* light = (const uint4*)p.light;
 
     uint32_t st2[8];
+    kp_seed(j.header, j.nonce, st2);
     {
-        uint32_t s[25];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) s[i] = j.header[i];
-        s[8] = (uint32_t)j.nonce;
-        s[9] = (uint32_t)(j.nonce >> 32);
-        const uint32_t pad[15] = {0x72, 0x41, 0x56, 0x45, 0x4E, 0x43, 0x4F, 0x49, 0x4E, 0x4B, 0x41, 0x57, 0x50, 0x4F, 0x57};
-#pragma unroll
-        for (int i = 0; i < 15; ++i) s[10 + i] = pad[i];
-        keccak_f800(s);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) st2[i] = s[i];
-    }
-    {
-        const uint32_t z0 = kl_fnv1a(0x811c9dc5u, st2[0]);
-        const uint32_t w0 = kl_fnv1a(z0, st2[1]);
-        const uint32_t jsr0 = kl_fnv1a(w0, lane);
-        uint32_t kz = z0, kw = w0, kj = jsr0, kc = kl_fnv1a(jsr0, lane);
-        for (int r = 0; r < 32; ++r) {
-            kz = 36969u * (kz & 0xffffu) + (kz >> 16);
-            kw = 18000u * (kw & 0xffffu) + (kw >> 16);
-            kc = 69069u * kc + 1234567u;
-            kj ^= (kj << 17);
-            kj ^= (kj >> 13);
-            kj ^= (kj << 5);
-            KL_MIX(r) = (((kz << 16) + kw) ^ kc) + kj;
-        }
+        KpKiss rng = kp_mix_rng(st2[0], st2[1], lane);
+        for (int r = 0; r < 32; ++r) KL_MIX(r) = rng.next();
     }
     const uint32_t q = lane >> 2, s = lane & 3;
     for (uint32_t r = 0; r < 64; ++r) {
-        const uint32_t index = kl_mod(__shfl(KL_MIX(0), (int)(r & 15), 16), p.items);
+        const uint32_t index = kp_mod(__shfl(KL_MIX(0), (int)(r & 15), 16), p.items);
         uint4 mine;
         if constexpr (DAG) {
             // lane l = 4q+s holds words 4l..4l+3 of the 2048-bit item: one coalesced 256 B load per group
@@ -206,49 +149,31 @@ NX_DEV void kl_verify(const KawpowLightParams& p) {
                                 (uint32_t)__shfl((int)mine.z, src, 16), (uint32_t)__shfl((int)mine.w, src, 16)};
         for (int i = 0; i < 18; ++i) {
             if (i < 11) {
-                const uint32_t op = prog[i];
-                const uint32_t a = KL_MIX(op & 31);
-                uint32_t& dst = KL_MIX((op >> 8) & 31);
-                dst = kl_merge(dst, l1[a & 4095u], (op >> 16) & 3, op >> 24);
+                const uint32_t op = prog[KP_PROG_CACHE + i];
+                const uint32_t a = KL_MIX(kp_cache_src(op));
+                uint32_t& dst = KL_MIX(kp_cache_dst(op));
+                dst = kp_merge(dst, l1[a & 4095u], kp_cache_kind(op), kp_cache_rot(op));
             }
-            const uint32_t op = prog[11 + i];
-            const uint32_t mg = prog[29 + i];
-            const uint32_t v = kl_math(KL_MIX(op & 31), KL_MIX((op >> 8) & 31), (op >> 16) & 15);
-            uint32_t& dst = KL_MIX(op >> 24);
-            dst = kl_merge(dst, v, mg & 3, mg >> 8);
+            const uint32_t op = prog[KP_PROG_MATH + i];
+            const uint32_t mg = prog[KP_PROG_MMERGE + i];
+            const uint32_t v = kp_math(KL_MIX(kp_math_src1(op)), KL_MIX(kp_math_src2(op)), kp_math_kind(op));
+            uint32_t& dst = KL_MIX(kp_math_dst(op));
+            dst = kp_merge(dst, v, kp_mmerge_kind(mg), kp_mmerge_rot(mg));
         }
         for (int i = 0; i < 4; ++i) {
-            const uint32_t op = prog[47 + i];
-            uint32_t& dst = KL_MIX(op & 31);
-            dst = kl_merge(dst, dw[i], (op >> 8) & 3, op >> 16);
+            const uint32_t op = prog[KP_PROG_DAG + i];
+            uint32_t& dst = KL_MIX(kp_dag_dst(op));
+            dst = kp_merge(dst, dw[i], kp_dag_kind(op), kp_dag_rot(op));
         }
     }
-    uint32_t lh = 0x811c9dc5u;
-    for (int r = 0; r < 32; ++r) lh = kl_fnv1a(lh, KL_MIX(r));
+    uint32_t lh = KP_FNV_OFFSET;
+    for (int r = 0; r < 32; ++r) lh = kp_fnv1a(lh, KL_MIX(r));
     uint32_t digest[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const uint32_t a = __shfl(lh, k, 16);
-        const uint32_t b = __shfl(lh, k + 8, 16);
-        digest[k] = kl_fnv1a(kl_fnv1a(0x811c9dc5u, a), b);
-    }
-    uint32_t st[25];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) st[i] = st2[i];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) st[8 + i] = digest[i];
-    const uint32_t pad[9] = {0x72, 0x41, 0x56, 0x45, 0x4E, 0x43, 0x4F, 0x49, 0x4E};
-#pragma unroll
-    for (int i = 0; i < 9; ++i) st[16 + i] = pad[i];
-    keccak_f800(st);
-    if (valid && lane == 0) {
-        uint32_t* o = p.out + (size_t)job * 16;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            o[k] = digest[k];
-            o[8 + k] = st[k];
-        }
-    }
+    for (int k = 0; k < 8; ++k) digest[k] = kp_digest_word(lh, k);
+    uint32_t fin[8];
+    kp_final(st2, digest, fin);
+    if (valid && lane == 0) kp_store_hash(p.out, job, digest, fin);
 }
 
 extern "C" __global__ __launch_bounds__(KL_BLOCK) void kawpow_verify_light(KawpowLightParams p) { kl_verify<false>(p); }
@@ -368,100 +293,61 @@ extern "C" __global__ __launch_bounds__(KL_BLOCK) void kawpow_verify_waves(Kawpo
     // the period's 51 op words, loaded once into SGPRs: inside the round loop every op word is a
     // literal SGPR (the loop below is unrolled), so no op waits on a scalar load -- and the LDS L1
     // lookups, which share the lgkm counter with scalar loads, no longer wait behind them either
-    uint32_t pw[51];
+    uint32_t pw[KP_PROG_OPS];
 #pragma unroll
-    for (int i = 0; i < 51; ++i) pw[i] = __builtin_amdgcn_readfirstlane(prog[i]);
+    for (int i = 0; i < KP_PROG_OPS; ++i) pw[i] = __builtin_amdgcn_readfirstlane(prog[i]);
     const KawpowVerifyJob j = p.jobs[jj];
 
     uint32_t st2[8];
-    {
-        uint32_t s[25];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) s[i] = j.header[i];
-        s[8] = (uint32_t)j.nonce;
-        s[9] = (uint32_t)(j.nonce >> 32);
-        const uint32_t pad[15] = {0x72, 0x41, 0x56, 0x45, 0x4E, 0x43, 0x4F, 0x49, 0x4E, 0x4B, 0x41, 0x57, 0x50, 0x4F, 0x57};
-#pragma unroll
-        for (int i = 0; i < 15; ++i) s[10 + i] = pad[i];
-        keccak_f800(s);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) st2[i] = s[i];
-    }
+    kp_seed(j.header, j.nonce, st2);
     kw_mix_t mix;
     {
-        const uint32_t z0 = kl_fnv1a(0x811c9dc5u, st2[0]);
-        const uint32_t w0 = kl_fnv1a(z0, st2[1]);
-        const uint32_t jsr0 = kl_fnv1a(w0, lane);
-        uint32_t kz = z0, kw = w0, kj = jsr0, kc = kl_fnv1a(jsr0, lane);
+        KpKiss rng = kp_mix_rng(st2[0], st2[1], lane);
 #pragma unroll
-        for (int r = 0; r < 32; ++r) {
-            kz = 36969u * (kz & 0xffffu) + (kz >> 16);
-            kw = 18000u * (kw & 0xffffu) + (kw >> 16);
-            kc = 69069u * kc + 1234567u;
-            kj ^= (kj << 17);
-            kj ^= (kj >> 13);
-            kj ^= (kj << 5);
-            mix[r] = (((kz << 16) + kw) ^ kc) + kj;
-        }
+        for (int r = 0; r < 32; ++r) mix[r] = rng.next();
     }
     const uint4* dag = (const uint4*)p.dag;
     uint32_t tlo, thi;
     kwt_table(tlo, thi);
 #pragma unroll 1
     for (uint32_t r = 0; r < 64; ++r) {
-        const uint32_t index = kl_mod(__shfl(mix[0], (int)(r & 15), 16), p.items);
+        const uint32_t index = kp_mod(__shfl(mix[0], (int)(r & 15), 16), p.items);
         // lane l merges words ((l^r)%16)*4..+3 of the 2048-bit item: load exactly that slice
         const uint4 d = dag[(size_t)index * 16 + ((lane ^ r) & 15)];
         // opaque per round: the op fields are decoded where they are used (SALU, next to the op)
         // instead of being hoisted out of the loop into ~150 loop-invariant SGPRs that spill
 #pragma unroll
-        for (int i = 0; i < 51; ++i) asm volatile("" : "+s"(pw[i]));
+        for (int i = 0; i < KP_PROG_OPS; ++i) asm volatile("" : "+s"(pw[i]));
 #pragma unroll
         for (int i = 0; i < 18; ++i) {
             if (i < 11) {
-                const uint32_t op = pw[i];
-                const uint32_t dst = (op >> 8) & 31;
-                kw_set(mix, dst, kwt_merge(tlo, thi, kw_get(mix, dst), l1[kw_get(mix, op) & 4095u], (op >> 16) & 3, op >> 24));
+                const uint32_t op = pw[KP_PROG_CACHE + i];
+                const uint32_t dst = kp_cache_dst(op);
+                kw_set(mix, dst, kwt_merge(tlo, thi, kw_get(mix, dst), l1[kw_get(mix, kp_cache_src(op)) & 4095u],
+                                           kp_cache_kind(op), kp_cache_rot(op)));
             }
-            const uint32_t op = pw[11 + i];
-            const uint32_t mg = pw[29 + i];
-            const uint32_t dst = op >> 24;
-            kw_set(mix, dst, kwt_op(tlo, thi, kw_get(mix, op), kw_get(mix, op >> 8), kw_get(mix, dst), (op >> 16) & 15,
-                                    mg & 3, mg >> 8));
+            const uint32_t op = pw[KP_PROG_MATH + i];
+            const uint32_t mg = pw[KP_PROG_MMERGE + i];
+            const uint32_t dst = kp_math_dst(op);
+            kw_set(mix, dst, kwt_op(tlo, thi, kw_get(mix, kp_math_src1(op)), kw_get(mix, kp_math_src2(op)), kw_get(mix, dst),
+                                    kp_math_kind(op), kp_mmerge_kind(mg), kp_mmerge_rot(mg)));
         }
         const uint32_t dw[4] = {d.x, d.y, d.z, d.w};
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const uint32_t op = pw[47 + i];
-            kw_set(mix, op, kwt_merge(tlo, thi, kw_get(mix, op), dw[i], (op >> 8) & 3, op >> 16));
+            const uint32_t op = pw[KP_PROG_DAG + i];
+            const uint32_t dst = kp_dag_dst(op);
+            kw_set(mix, dst, kwt_merge(tlo, thi, kw_get(mix, dst), dw[i], kp_dag_kind(op), kp_dag_rot(op)));
         }
     }
-    uint32_t lh = 0x811c9dc5u;
+    uint32_t lh = KP_FNV_OFFSET;
 #pragma unroll
-    for (int r = 0; r < 32; ++r) lh = kl_fnv1a(lh, mix[r]);
+    for (int r = 0; r < 32; ++r) lh = kp_fnv1a(lh, mix[r]);
     uint32_t digest[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const uint32_t a = __shfl(lh, k, 16);
-        const uint32_t b = __shfl(lh, k + 8, 16);
-        digest[k] = kl_fnv1a(kl_fnv1a(0x811c9dc5u, a), b);
-    }
-    uint32_t st[25];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) st[i] = st2[i];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) st[8 + i] = digest[i];
-    const uint32_t pad[9] = {0x72, 0x41, 0x56, 0x45, 0x4E, 0x43, 0x4F, 0x49, 0x4E};
-#pragma unroll
-    for (int i = 0; i < 9; ++i) st[16 + i] = pad[i];
-    keccak_f800(st);
-    if (valid && lane == 0) {
-        uint32_t* o = p.out + (size_t)row * 16;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            o[k] = digest[k];
-            o[8 + k] = st[k];
-        }
-    }
+    for (int k = 0; k < 8; ++k) digest[k] = kp_digest_word(lh, k);
+    uint32_t fin[8];
+    kp_final(st2, digest, fin);
+    if (valid && lane == 0) kp_store_hash(p.out, (uint32_t)row, digest, fin);
 }
 

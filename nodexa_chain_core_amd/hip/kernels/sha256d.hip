@@ -10,8 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "kernel_params.h"
-#include "keccak_device.hpp"
+#include "kawpow_device.hpp"
 #include "sha256_device.hpp"
 
 // SHA-256 of len bytes at m (any alignment), padding generated on the fly. A block that lies
@@ -120,27 +119,13 @@ extern "C" __global__ __launch_bounds__(256) void kawpow_mixonly_batch(MixOnlyPa
     sha256_bytes(h, 80, s1);
     sha256_of_digest(s1, s2);
     // ProgPoW word k of the byte-reversed digest is SHA state word 7-k (its big-endian bytes reversed)
-    uint32_t st[25];
+    uint32_t hh[8], st2[8], mix[8], st[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) st[k] = s2[7 - k];
-    st[8] = mo_le32(h + 80);   // nonce64 low
-    st[9] = mo_le32(h + 84);   // nonce64 high
-    const uint32_t pad1[15] = {0x72, 0x41, 0x56, 0x45, 0x4E, 0x43, 0x4F, 0x49, 0x4E, 0x4B, 0x41, 0x57, 0x50, 0x4F, 0x57};
-#pragma unroll
-    for (int k = 0; k < 15; ++k) st[10 + k] = pad1[k];
-    uint32_t hh[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) hh[k] = st[k];
-    keccak_f800(st);
-    uint32_t mix[8];
+    for (int k = 0; k < 8; ++k) hh[k] = s2[7 - k];
+    kp_seed(hh, (uint64_t(mo_le32(h + 84)) << 32) | mo_le32(h + 80), st2);  // nonce64
 #pragma unroll
     for (int k = 0; k < 8; ++k) mix[k] = __builtin_bswap32(mo_le32(h + 88 + 28 - 4 * k));  // reversed mix_hash
-#pragma unroll
-    for (int k = 0; k < 8; ++k) st[8 + k] = mix[k];  // st[0..7] = seed state words
-    const uint32_t pad2[9] = {0x72, 0x41, 0x56, 0x45, 0x4E, 0x43, 0x4F, 0x49, 0x4E};
-#pragma unroll
-    for (int k = 0; k < 9; ++k) st[16 + k] = pad2[k];
-    keccak_f800(st);
+    kp_final(st2, mix, st);
     // nBits -> 256-bit target, big-endian bytes (arith_uint256::SetCompact; zero when negative or
     // overflowing, so nothing meets it)
     const uint32_t bits = mo_le32(h + 72);

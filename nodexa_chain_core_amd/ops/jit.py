@@ -15,6 +15,7 @@ from __future__ import annotations
 import concurrent.futures as cf
 import hashlib
 import os
+import re
 import subprocess
 import tempfile
 import threading
@@ -28,11 +29,30 @@ _lock = threading.Lock()
 _inflight: dict[tuple, cf.Future] = {}
 
 
-def _template_digest() -> str:
-    h = hashlib.sha256()
-    kdir = os.path.join(_build.HIPDIR, "kernels")
-    for name in ("kawpow_search.hip", "kernel_params.h", "keccak_device.hpp"):
+_INCLUDE = re.compile(rb'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', re.M)
+
+
+def template_files(template: str | None = None) -> list[str]:
+    """The template and every project file it includes, directly or not: `#include "..."` followed
+    inside the template's directory, each file once, in the order first met. The period's program
+    (`#include KAWPOW_PROGRAM_HEADER`) names no file here; object_path keys it by its text."""
+    template = TEMPLATE if template is None else template
+    kdir = os.path.dirname(template)
+    files, todo = [], [os.path.basename(template)]
+    while todo:
+        name = todo.pop(0)
+        if name in files:
+            continue
+        files.append(name)
         with open(os.path.join(kdir, name), "rb") as f:
+            todo += [m.decode() for m in _INCLUDE.findall(f.read())]
+    return [os.path.join(kdir, name) for name in files]
+
+
+def _template_digest(template: str | None = None) -> str:
+    h = hashlib.sha256()
+    for path in template_files(template):
+        with open(path, "rb") as f:
             h.update(f.read())
     h.update(_build.ARCH.encode())
     return h.hexdigest()[:16]

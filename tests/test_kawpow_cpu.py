@@ -134,6 +134,33 @@ def test_search_variant_selection_by_dag_size(core):
     assert jit.defines_for(above, ("KP_SBUFFER", "KP_DPP")) == ("KP_PTR64", "KP_DPP")
 
 
+def test_template_digest_covers_every_included_file(core, tmp_path):
+    """ops/jit: the per-period cache key follows the template's `#include "..."` lines, so a byte
+    changed in any project file the template pulls in (or in the template) names a new code object
+    instead of serving a stale one from the kernel cache. No compiler involved."""
+    import os
+    import shutil
+
+    from nodexa_chain_core_amd.ops import jit
+
+    kdir = tmp_path / "kernels"
+    shutil.copytree(os.path.dirname(jit.TEMPLATE), kdir)
+    template = str(kdir / os.path.basename(jit.TEMPLATE))
+    names = [os.path.basename(p) for p in jit.template_files(template)]
+    assert names[0] == "kawpow_search.hip" and len(names) == len(set(names))
+    assert {"kawpow_device.hpp", "keccak_device.hpp", "kernel_params.h"} <= set(names)
+    assert jit._template_digest(template) == jit._template_digest()  # the copy is the tree's
+    seen = {jit._template_digest(template)}
+    for name in ("kawpow_device.hpp", "keccak_device.hpp", "kernel_params.h", "kawpow_search.hip"):
+        with open(kdir / name, "ab") as f:
+            f.write(b"\n")
+        seen.add(jit._template_digest(template))
+    assert len(seen) == 5  # every change moved the digest, each to a value of its own
+    with open(kdir / "sha256d.hip", "ab") as f:  # not included by the template: not in the key
+        f.write(b"\n")
+    assert jit._template_digest(template) in seen
+
+
 
 
 def test_prefetch_contexts_builds_in_parallel(core):

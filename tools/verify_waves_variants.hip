@@ -149,7 +149,7 @@ NX_DEV uint32_t pv_merge(uint32_t a, uint32_t b, uint32_t kind, uint32_t rot) {
     } else if constexpr (V == 6 || V == 7) {
         return pj_merge(a, b, kind, rot);
     } else {
-        return kl_merge(a, b, kind, rot);
+        return kp_merge(a, b, kind, rot);
     }
 }
 
@@ -157,7 +157,7 @@ template <int V>
 NX_DEV uint32_t pv_math(uint32_t a, uint32_t b, uint32_t kind) {
     if constexpr (V == 2) return a ^ b;
     else if constexpr (V == 6 || V == 8) return pj_math(a, b, kind);
-    else return kl_math(a, b, kind);
+    else return kp_math(a, b, kind);
 }
 
 template <int V>
@@ -176,40 +176,17 @@ NX_DEV void pv_waves(const KawpowLightParams& p) {
     uint32_t pi = __builtin_amdgcn_readfirstlane(p.job_program[first]);
     pi = pi < p.num_programs ? pi : 0;
     const uint32_t* prog = p.programs + (size_t)pi * KV_PROG_WORDS;
-    uint32_t pw[51];
+    uint32_t pw[KP_PROG_OPS];
 #pragma unroll
-    for (int i = 0; i < 51; ++i) pw[i] = __builtin_amdgcn_readfirstlane(prog[i]);
+    for (int i = 0; i < KP_PROG_OPS; ++i) pw[i] = __builtin_amdgcn_readfirstlane(prog[i]);
     const KawpowVerifyJob j = p.jobs[jj];
     uint32_t st2[8];
-    {
-        uint32_t s[25];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) s[i] = j.header[i];
-        s[8] = (uint32_t)j.nonce;
-        s[9] = (uint32_t)(j.nonce >> 32);
-        const uint32_t pad[15] = {0x72, 0x41, 0x56, 0x45, 0x4E, 0x43, 0x4F, 0x49, 0x4E, 0x4B, 0x41, 0x57, 0x50, 0x4F, 0x57};
-#pragma unroll
-        for (int i = 0; i < 15; ++i) s[10 + i] = pad[i];
-        keccak_f800(s);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) st2[i] = s[i];
-    }
+    kp_seed(j.header, j.nonce, st2);
     kw_mix_t mix;
     {
-        const uint32_t z0 = kl_fnv1a(0x811c9dc5u, st2[0]);
-        const uint32_t w0 = kl_fnv1a(z0, st2[1]);
-        const uint32_t jsr0 = kl_fnv1a(w0, lane);
-        uint32_t kz = z0, kw = w0, kj = jsr0, kc = kl_fnv1a(jsr0, lane);
+        KpKiss rng = kp_mix_rng(st2[0], st2[1], lane);
 #pragma unroll
-        for (int r = 0; r < 32; ++r) {
-            kz = 36969u * (kz & 0xffffu) + (kz >> 16);
-            kw = 18000u * (kw & 0xffffu) + (kw >> 16);
-            kc = 69069u * kc + 1234567u;
-            kj ^= (kj << 17);
-            kj ^= (kj >> 13);
-            kj ^= (kj << 5);
-            mix[r] = (((kz << 16) + kw) ^ kc) + kj;
-        }
+        for (int r = 0; r < 32; ++r) mix[r] = rng.next();
     }
     const uint4* dag = (const uint4*)p.dag;
     uint32_t tlo = 0, thi = 0;
@@ -217,17 +194,17 @@ NX_DEV void pv_waves(const KawpowLightParams& p) {
     if constexpr (V == 10) kwt2_table(tlo, thi);
 #pragma unroll 1
     for (uint32_t r = 0; r < 64; ++r) {
-        const uint32_t index = kl_mod(__shfl(mix[0], (int)(r & 15), 16), p.items);
+        const uint32_t index = kp_mod(__shfl(mix[0], (int)(r & 15), 16), p.items);
         uint4 d;
         if constexpr (V == 3) d = make_uint4(index, index + 1, index + 2, index + 3);
         else d = dag[(size_t)index * 16 + ((lane ^ r) & 15)];
 #pragma unroll
-        for (int i = 0; i < 51; ++i) asm volatile("" : "+s"(pw[i]));
+        for (int i = 0; i < KP_PROG_OPS; ++i) asm volatile("" : "+s"(pw[i]));
         if constexpr (V == 10) {
 #pragma unroll
             for (int i = 0; i < 18; ++i) {
-                const uint32_t op = pw[11 + i];
-                const uint32_t mg = pw[29 + i];
+                const uint32_t op = pw[KP_PROG_MATH + i];
+                const uint32_t mg = pw[KP_PROG_MMERGE + i];
                 const uint32_t dst = op >> 24;
                 if (i < 11) {
                     const uint32_t opc = pw[i];
@@ -249,7 +226,7 @@ NX_DEV void pv_waves(const KawpowLightParams& p) {
             const uint32_t dw[4] = {d.x, d.y, d.z, d.w};
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const uint32_t op = pw[47 + i];
+                const uint32_t op = pw[KP_PROG_DAG + i];
                 kw_set(mix, op, kwt_merge(tlo, thi, kw_get(mix, op), dw[i], (op >> 8) & 3, op >> 16));
             }
             continue;
@@ -262,8 +239,8 @@ NX_DEV void pv_waves(const KawpowLightParams& p) {
                     const uint32_t dst = (op >> 8) & 31;
                     kw_set(mix, dst, kwt_merge(tlo, thi, kw_get(mix, dst), l1[kw_get(mix, op) & 4095u], (op >> 16) & 3, op >> 24));
                 }
-                const uint32_t op = pw[11 + i];
-                const uint32_t mg = pw[29 + i];
+                const uint32_t op = pw[KP_PROG_MATH + i];
+                const uint32_t mg = pw[KP_PROG_MMERGE + i];
                 const uint32_t dst = op >> 24;
                 kw_set(mix, dst, kwt_op(tlo, thi, kw_get(mix, op), kw_get(mix, op >> 8), kw_get(mix, dst), (op >> 16) & 15,
                                         mg & 3, mg >> 8));
@@ -271,7 +248,7 @@ NX_DEV void pv_waves(const KawpowLightParams& p) {
             const uint32_t dw[4] = {d.x, d.y, d.z, d.w};
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const uint32_t op = pw[47 + i];
+                const uint32_t op = pw[KP_PROG_DAG + i];
                 kw_set(mix, op, kwt_merge(tlo, thi, kw_get(mix, op), dw[i], (op >> 8) & 3, op >> 16));
             }
             continue;
@@ -286,8 +263,8 @@ NX_DEV void pv_waves(const KawpowLightParams& p) {
                 const uint32_t look = V == 1 ? a : l1[a & 4095u];
                 kw_set(mix, dst, pv_merge<V>(kw_get(mix, dst), look, (op >> 16) & 3, op >> 24));
             }
-            const uint32_t op = pw[11 + i];
-            const uint32_t mg = pw[29 + i];
+            const uint32_t op = pw[KP_PROG_MATH + i];
+            const uint32_t mg = pw[KP_PROG_MMERGE + i];
             const uint32_t s1 = V == 4 ? (uint32_t)((i * 3 + 2) & 31) : op;
             const uint32_t s2 = V == 4 ? (uint32_t)((i * 11 + 5) & 31) : (op >> 8);
             const uint32_t dst = V == 4 ? (uint32_t)((i * 13 + 7) & 31) : (op >> 24);
@@ -297,38 +274,19 @@ NX_DEV void pv_waves(const KawpowLightParams& p) {
         const uint32_t dw[4] = {d.x, d.y, d.z, d.w};
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const uint32_t op = pw[47 + i];
+            const uint32_t op = pw[KP_PROG_DAG + i];
             const uint32_t dst = V == 4 ? (uint32_t)(i * 8) : op;
             kw_set(mix, dst, pv_merge<V>(kw_get(mix, dst), dw[i], (op >> 8) & 3, op >> 16));
         }
     }
-    uint32_t lh = 0x811c9dc5u;
+    uint32_t lh = KP_FNV_OFFSET;
 #pragma unroll
-    for (int r = 0; r < 32; ++r) lh = kl_fnv1a(lh, mix[r]);
-    uint32_t digest[8];
+    for (int r = 0; r < 32; ++r) lh = kp_fnv1a(lh, mix[r]);
+    uint32_t digest[8], fin[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const uint32_t a = __shfl(lh, k, 16);
-        const uint32_t b = __shfl(lh, k + 8, 16);
-        digest[k] = kl_fnv1a(kl_fnv1a(0x811c9dc5u, a), b);
-    }
-    uint32_t st[25];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) st[i] = st2[i];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) st[8 + i] = digest[i];
-    const uint32_t pad[9] = {0x72, 0x41, 0x56, 0x45, 0x4E, 0x43, 0x4F, 0x49, 0x4E};
-#pragma unroll
-    for (int i = 0; i < 9; ++i) st[16 + i] = pad[i];
-    keccak_f800(st);
-    if (valid && lane == 0) {
-        uint32_t* o = p.out + (size_t)row * 16;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            o[k] = digest[k];
-            o[8 + k] = st[k];
-        }
-    }
+    for (int k = 0; k < 8; ++k) digest[k] = kp_digest_word(lh, k);
+    kp_final(st2, digest, fin);
+    if (valid && lane == 0) kp_store_hash(p.out, (uint32_t)row, digest, fin);
 }
 
 #define PV(n) extern "C" __global__ __launch_bounds__(KL_BLOCK) void pv_waves_##n(KawpowLightParams p) { pv_waves<n>(p); }
