@@ -39,6 +39,24 @@ Nonce ranges: an extranonce of b bytes leaves `free = 64 - 8b` low bits. A work 
 `rank_shift` s (miner/search.Work): rank r of the mining loop owns
 [nonce_base + (r << s), nonce_base + ((r + 1) << s)), and `rank_shift_for` picks
 s = free - ceil(log2(world_size)), at most 63 (an empty extranonce leaves 64 free bits).
+
+Vardiff (the server's -stratumvardiff=<shares per minute>; `vardiff_next_bits`; this is the only
+place the rule is written down). Every connection has share bits of its own, n, meaning the share
+target 2^(256-n) - 1 (`share_target_for_bits`); it starts at lo_bits = -stratumsharebits, the easiest
+target it can ever have, and never exceeds hi_bits = 255 (the job's block target still wins where it
+is easier). A retarget looks at `shares`, the shares accepted since the connection's last retarget
+(or its mining.authorize), and `elapsed_ms`, the time since then, in integers only:
+    E = per_minute * elapsed_ms     (the wanted shares, times 60000)
+    S = shares * 60000              (the shares there were, times the same)
+    S >= 2E:  bits += min(4, floor(log2(S / E)))   too many shares: a harder target
+    2S <= E:  bits -= min(4, floor(log2(E / S)))   too few: an easier one; shares == 0 counts as 4
+    otherwise unchanged; then clamped to [lo_bits, hi_bits].
+floor(log2(a / b)) is the largest k with a >= b * 2^k, found by shifting: no division, no float.
+E == 0 (no time passed, or a rate of 0) measures nothing and leaves the bits as they are. One step
+changes the target by at most 2^4, and inside (1/2, 2) of the wanted rate nothing moves, so a
+connection near the wanted rate is left alone. When the rule runs is the server's business
+(miner/stratum_server.py): only together with a job, so that a new target always travels as
+mining.set_target in front of a mining.notify.
 """
 from __future__ import annotations
 
@@ -113,6 +131,34 @@ def parse_extranonce(s) -> bytes:
 def share_target_for_bits(bits: int) -> int:
     """-stratumsharebits=n: 2^(256-n) - 1, the definition -minertargetbits uses."""
     return (1 << (256 - int(bits))) - 1
+
+
+VARDIFF_MAX_STEP = 4   # bits per retarget, either way
+VARDIFF_MAX_BITS = 255
+
+
+def _floor_log2_ratio(a: int, b: int, cap: int) -> int:
+    """min(cap, floor(log2(a / b))) for a >= b > 0: the largest k <= cap with a >= b << k."""
+    k = 0
+    while k < cap and a >= b << (k + 1):
+        k += 1
+    return k
+
+
+def vardiff_next_bits(bits: int, shares: int, elapsed_ms: int, per_minute: int, lo_bits: int,
+                      hi_bits: int = VARDIFF_MAX_BITS) -> int:
+    """A connection's next share bits (the rule: module docstring). Integers only."""
+    bits, shares, elapsed_ms, per_minute = int(bits), int(shares), int(elapsed_ms), int(per_minute)
+    if shares < 0 or elapsed_ms < 0 or per_minute < 0:
+        raise ValueError("vardiff: shares, elapsed_ms and per_minute must not be negative")
+    e = per_minute * elapsed_ms
+    s = shares * 60000
+    if e > 0:
+        if s >= 2 * e:
+            bits += _floor_log2_ratio(s, e, VARDIFF_MAX_STEP)
+        elif 2 * s <= e:
+            bits -= VARDIFF_MAX_STEP if s == 0 else _floor_log2_ratio(e, s, VARDIFF_MAX_STEP)
+    return max(int(lo_bits), min(int(hi_bits), bits))
 
 
 # ---------------------------------------------------------------------- nonce ranges

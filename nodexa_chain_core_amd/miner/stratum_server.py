@@ -6,21 +6,43 @@ Threads:
   checks, and writing. Other threads only append to a connection's bounded send buffer and wake
   the selector; a connection whose buffer is full (a peer that does not read) is closed, so no slow
   or dead peer can hold up the verifier or the other connections;
-* the job thread waits for the job source to change and pushes `mining.notify` to everybody;
+* the job thread waits for the job source to change and pushes `mining.notify` to everybody; with
+  vardiff it also sends the current job again (clean_jobs false) to a connection that got no job
+  for `RESEND_S` and whose target is due to change;
 * the verifier thread does the full hashes. It drains whatever submits are queued at that moment
   into one batch (no added wait: batching comes from submits that arrive while a batch runs). A
-  job whose epoch DAG is resident on the node's device (ops/verify.is_resident: the one the miner
-  built) goes through ops/verify.gpu_full_hash, anything else through the host's light-mode
-  `_core.kawpow_hash`; it never builds a DAG for a share check.
+  job whose epoch DAG is resident on the node's device (ops/verify.is_resident) goes through
+  ops/verify.gpu_full_hash, anything else through the host's light-mode `_core.kawpow_hash`. The
+  verifier itself never builds a DAG and never waits for one;
+* with `gpu_verify` (-stratumgpuverify=1) and a device, one more thread (miner/stratum_epochs.py)
+  builds the DAG of the current job's epoch when none is resident (a node that serves rigs without
+  mining itself, or whose miner has not shared the new epoch yet), and the next epoch's from 120
+  blocks before the boundary. While it builds, the epoch's shares go through `gpu_full_hash` in
+  light mode as soon as the light cache is on the device, and through the host before that.
+  Without the flag the only resident DAGs are the ones the in-process miner built.
 
 `mining.submit` is checked in this order, answering at the first failure: subscribed (25) and
-authorized (24); job known and built on the current tip (21); header hash equals the job's (20);
-nonce carries the connection's extranonce (20); (job, nonce) not seen before (22);
-`kawpow_hash_no_verify(height, header, mix, nonce)` at or below the share target (23: the cheap
-check, no DAG access); the recomputed mix equals the submitted one (otherwise 20 and the connection
-is closed: an honest miner cannot produce that). A share whose job went stale while it waited for
-its full hash is answered 21 then. A share whose final hash also meets the block target becomes a
-block through the job source.
+authorized (24); job known, built on the current tip and, with vardiff, sent to this connection
+(21); header hash equals the job's (20); nonce carries the connection's extranonce (20); (job,
+nonce) not seen before (22); `kawpow_hash_no_verify(height, header, mix, nonce)` at or below the
+share target (23: the cheap check, no DAG access); the recomputed mix equals the submitted one
+(otherwise 20 and the connection is closed: an honest miner cannot produce that). A share whose job
+went stale while it waited for its full hash is answered 21 then. A share whose final hash also
+meets the block target becomes a block through the job source.
+
+The share target is the easier of the block target and 2^(256-bits) - 1. Without vardiff, bits is
+-stratumsharebits for everybody. With `vardiff` (-stratumvardiff=<shares per minute>) every
+connection has bits of its own, starting at -stratumsharebits; the rule is miner/stratum.py's
+`vardiff_next_bits`. It runs only when a job is about to go to the connection and `RETARGET_S` have
+passed since its last retarget (or its authorize), so a new target always travels as
+`mining.set_target` right in front of a `mining.notify`, and a share is judged against the target
+that went out with its job to that connection (the last `JOBS_KEPT` jobs are remembered per
+connection; where the same job went out twice, the easier target judges and the work credited is
+that of the hardest target sent that the hash meets). Every accepted share is recorded with its
+work, 2^256 / (target + 1), and a connection's hashrate is the work of its window over the window.
+
+`ban_s` (-stratumbantime=<seconds>): an address whose connections were closed for a wrong mix
+`BAN_STRIKES` times within `BAN_WINDOW_S` is refused at accept for that long (`BanTable`).
 
 Jobs come from a `JobSource`: the current job, and wait for change. The node's `ChainJobSource`
 builds one template per job with BlockAssembler (all connections work on the same header hash in
@@ -49,6 +71,52 @@ EXTRANONCE_BYTES = 2
 SEND_BUFFER_MAX = 64 * 1024   # bytes queued for one connection before it is closed as too slow
 JOBS_KEPT = 8
 HASHRATE_WINDOW_S = 600.0
+RETARGET_S = 30.0      # vardiff: the least time between two retargets of a connection
+RESEND_S = 60.0        # vardiff: a connection without a job for this long gets the current one again when a retarget is due
+BAN_STRIKES = 3        # -stratumbantime: wrong mixes from one address ...
+BAN_WINDOW_S = 600.0   # ... within this time
+BAN_TABLE_MAX = 1024   # addresses remembered, the oldest dropped
+
+
+def share_work(target: int) -> int:
+    """The expected hashes behind one share at `target`."""
+    return (1 << 256) // (target + 1)
+
+
+class BanTable:
+    """Addresses that sent wrong mixes. `strike(addr, now)` records one and returns True when it
+    is the `BAN_STRIKES`-th within `BAN_WINDOW_S`: the address is then banned for `ban_s`. One
+    table, bounded at `BAN_TABLE_MAX` addresses (strikes and bans together), oldest dropped."""
+
+    def __init__(self, ban_s: float):
+        self.ban_s = float(ban_s)
+        self.entries: collections.OrderedDict[str, list] = collections.OrderedDict()  # addr -> [strike times, banned until]
+        self.lock = threading.Lock()
+
+    def strike(self, addr: str, now: float) -> bool:
+        with self.lock:
+            ent = self.entries.pop(addr, None) or [[], 0.0]
+            ent[0] = [t for t in ent[0] if now - t < BAN_WINDOW_S] + [now]
+            banned = len(ent[0]) >= BAN_STRIKES
+            if banned:
+                ent[:] = [[], now + self.ban_s]
+            self.entries[addr] = ent  # most recent last
+            while len(self.entries) > BAN_TABLE_MAX:
+                self.entries.popitem(last=False)
+            return banned
+
+    def banned_until(self, addr: str, now: float) -> float:
+        """When the address's ban ends, or 0.0 when it has none."""
+        with self.lock:
+            ent = self.entries.get(addr)
+            if ent is None or ent[1] <= now:
+                if ent is not None and not ent[0] and ent[1]:
+                    del self.entries[addr]  # an expired ban with no strike since
+                return 0.0
+            return ent[1]
+
+    def __len__(self) -> int:
+        return len(self.entries)
 
 
 @dataclass
@@ -267,7 +335,7 @@ class ChainJobSource(JobSource):
 
 
 class _Conn:
-    def __init__(self, cid: int, sock, addr, extranonce: bytes):
+    def __init__(self, cid: int, sock, addr, extranonce: bytes, now: float | None = None, bits: int = 0):
         self.id = cid
         self.sock = sock
         self.addr = addr
@@ -281,40 +349,71 @@ class _Conn:
         self.authorized = False
         self.agent = ""
         self.user = ""
-        self.connected = time.time()
+        self.connected = time.time() if now is None else now
         self.accepted = 0
         self.rejected: dict[int, int] = {}
         self.last_share = 0.0
         self.accept_times: collections.deque = collections.deque()
         self.target_sent: int | None = None
         self.job_sent: ServerJob | None = None
+        self.job_sent_at = 0.0
+        # vardiff (unused without it): the connection's share bits, the shares accepted and the time since
+        # its last retarget, and the targets that went out to it with each of its last JOBS_KEPT jobs
+        self.bits = bits
+        self.retargets = 0
+        self.retarget_at = self.connected
+        self.shares_since = 0
+        self.job_targets: collections.OrderedDict[str, list[int]] = collections.OrderedDict()
 
-    def info(self, share_target: int, now: float) -> dict:
-        while self.accept_times and now - self.accept_times[0] > HASHRATE_WINDOW_S:
+    def info(self, now: float) -> dict:
+        """`accept_times` holds (time, work of that share's target): the hashrate is the window's work."""
+        while self.accept_times and now - self.accept_times[0][0] > HASHRATE_WINDOW_S:
             self.accept_times.popleft()
         span = max(1e-3, min(now - self.connected, HASHRATE_WINDOW_S))
         return {"id": self.id, "address": f"{self.addr[0]}:{self.addr[1]}", "agent": self.agent, "user": self.user,
                 "extranonce": self.extranonce.hex(), "connected": round(now - self.connected, 3),
                 "accepted": self.accepted, "rejected": {str(k): v for k, v in sorted(self.rejected.items())},
                 "last_share": int(self.last_share),
-                "hashrate": round(len(self.accept_times) * (1 << 256) / (share_target + 1) / span, 3)}
+                "hashrate": round(sum(w for _t, w in self.accept_times) / span, 3),
+                "share_bits": self.bits, "retargets": self.retargets,
+                "shares_per_minute": round(len(self.accept_times) * 60.0 / span, 3)}
 
 
 class StratumServer:
     def __init__(self, source: JobSource, *, host: str = "127.0.0.1", port: int = 0, share_bits: int = 0,
-                 password: str | None = None, max_connections: int = 64, device: int | None = None):
+                 password: str | None = None, max_connections: int = 64, device: int | None = None,
+                 vardiff: int = 0, gpu_verify: bool = False, ban_s: float = 0.0, dag_check: bool = True,
+                 epoch_owner=None, clock=time.time):
+        """`vardiff`: wanted shares per minute and connection (0: one target for everybody).
+        `gpu_verify`: keep DAGs for share checks on `device` (an `EpochOwner`; `epoch_owner` injects
+        one). `ban_s`: seconds an address is refused after `BAN_STRIKES` wrong mixes (0: never).
+        `clock`: the time source of everything the server times (tests inject one)."""
         self.source = source
         self.host, self.port = host, int(port)
+        self.share_bits = int(share_bits)
+        self.vardiff = max(0, int(vardiff))
+        if self.vardiff and not 0 < self.share_bits <= S.VARDIFF_MAX_BITS:
+            raise ValueError("vardiff needs share bits above 0: they are where every connection starts "
+                             "and the easiest target it can get")
+        self.clock = clock
+        self.bans = BanTable(ban_s) if ban_s and ban_s > 0 else None
         self.share_target = S.share_target_for_bits(share_bits) if share_bits else 0  # 0: the block target
         self.password = password or None
         # every live connection needs a 2-byte extranonce of its own: below 2^16, so _accept always finds a free one
         self.max_connections = max(0, min(int(max_connections), (1 << 8 * EXTRANONCE_BYTES) - 1))
         self.device = device
+        self.epochs = epoch_owner
+        if self.epochs is None and gpu_verify and device is not None:
+            from .stratum_epochs import EpochOwner, device_builder
+
+            self.epochs = EpochOwner(device, device_builder(device, dag_check))
         self.conns: dict[int, _Conn] = {}
         self.lock = threading.Lock()       # conns, extranonces, counters
         self.stats = {"verify_batches_gpu": 0, "verify_batches_host": 0, "verified_gpu": 0, "verified_host": 0,
                       "accepted": 0, "rejected": 0, "refused_connections": 0, "jobs_sent": 0, "slow_closed": 0,
                       "blocks_rejected": 0}
+        if self.epochs is not None:
+            self.stats["verified_gpu_light"] = 0
         self.blocks_found = 0
         self.recent: collections.deque = collections.deque(maxlen=8)  # the last closed connections, as they ended
         self.verify_q: queue.Queue = queue.Queue()
@@ -356,6 +455,8 @@ class StratumServer:
         for t in self._threads:
             t.join(timeout)
         self._threads = []
+        if self.epochs is not None:
+            self.epochs.stop()
         for c in list(self.conns.values()):
             self._close(c)
         if self._listen is not None:
@@ -397,8 +498,35 @@ class StratumServer:
         """The easier of the share target and the block target."""
         return max(self.share_target, job.block_target)
 
+    def _next_bits(self, c: _Conn, now: float) -> int | None:
+        """The connection's bits after a retarget now, or None when none is due yet."""
+        if now - c.retarget_at < RETARGET_S:
+            return None
+        return S.vardiff_next_bits(c.bits, c.shares_since, int((now - c.retarget_at) * 1000), self.vardiff,
+                                   self.share_bits)
+
+    def _vardiff_target(self, c: _Conn, job: ServerJob, now: float) -> int:
+        """Vardiff's part of `_send_job`: retarget if due, and remember the target with the job."""
+        with self.lock:
+            bits = self._next_bits(c, now)
+            if bits is not None:
+                c.retarget_at, c.shares_since = now, 0
+                if bits != c.bits:
+                    c.bits = bits
+                    c.retargets += 1
+            target = max(S.share_target_for_bits(c.bits), job.block_target)
+            sent = c.job_targets.pop(job.job_id, [])
+            c.job_targets[job.job_id] = sent if target in sent else sent + [target]
+            while len(c.job_targets) > JOBS_KEPT:
+                c.job_targets.popitem(last=False)
+        return target
+
     def _send_job(self, c: _Conn, job: ServerJob, clean: bool | None = None) -> None:
-        target = self.effective_target(job)
+        if self.vardiff:
+            c.job_sent_at = now = self.clock()
+            target = self._vardiff_target(c, job, now)
+        else:
+            target = self.effective_target(job)
         wire = S.Job(job.job_id, job.header_hash, job.seed_hash, target, job.clean if clean is None else clean,
                      job.height, job.bits)
         data = b""
@@ -416,15 +544,29 @@ class StratumServer:
         while not self._stop.is_set():
             seq = self.source.wait_change(seq, 0.5)
             job = self.source.current()
+            if job is not None and job is last and self.vardiff:
+                self._resend_due(job)
             if job is None or job is last:
                 last = job
                 continue
             last = job
+            if self.epochs is not None:
+                self.epochs.note_job(job.height)
             with self.lock:
                 conns = [c for c in self.conns.values() if c.subscribed and c.authorized]
             for c in conns:
                 if c.job_sent is not job:  # it authorized after the change and got this job then
                     self._send_job(c, job)
+
+    def _resend_due(self, job: ServerJob) -> None:
+        """A connection that got no job for RESEND_S and whose bits a retarget would change now gets
+        the current job again, not clean: the only way a target reaches a connection is with a job."""
+        now = self.clock()
+        with self.lock:
+            due = [c for c in self.conns.values() if c.subscribed and c.authorized and c.job_sent is not None
+                   and now - c.job_sent_at >= RESEND_S and self._next_bits(c, now) not in (None, c.bits)]
+        for c in due:
+            self._send_job(c, job, clean=False)
 
     # ------------------------------------------------------------------ the I/O thread
     def _io_loop(self) -> None:
@@ -457,13 +599,20 @@ class StratumServer:
                 self.stats["refused_connections"] += 1
                 sock.close()
                 return
+            until = self.bans.banned_until(addr[0], self.clock()) if self.bans is not None else 0.0
+            if until:
+                self.stats["refused_connections"] += 1
+                self.recent.append({"address": f"{addr[0]}:{addr[1]}", "refused": "banned for wrong mixes",
+                                    "banned_until": int(until), "closed": int(self.clock())})
+                sock.close()
+                return
             used = {c.extranonce for c in self.conns.values()}
             while True:  # unique among the live connections
                 x = (self._next_extranonce & 0xFFFF).to_bytes(EXTRANONCE_BYTES, "big")
                 self._next_extranonce += 1
                 if x not in used:
                     break
-            c = _Conn(self._next_id, sock, addr, x)
+            c = _Conn(self._next_id, sock, addr, x, self.clock(), self.share_bits)
             self._next_id += 1
             self.conns[c.id] = c
         sock.setblocking(False)
@@ -481,7 +630,7 @@ class StratumServer:
         with self.lock:
             self.conns.pop(c.id, None)
             if c.subscribed:
-                self.recent.append(dict(c.info(self._info_target(), time.time()), closed=int(time.time())))
+                self.recent.append(dict(c.info(self.clock()), closed=int(self.clock())))
         try:
             self._sel.unregister(c.sock)
         except (KeyError, ValueError, OSError):
@@ -556,6 +705,7 @@ class StratumServer:
                     self._send(c, S.error_response(m.id, S.ERR_UNAUTHORIZED))
                     return
                 c.authorized, c.user = True, user[:64]
+                c.retarget_at = self.clock()
                 self._send(c, S.response(m.id, True))
                 job = self.source.current()
                 if job is not None:
@@ -578,18 +728,26 @@ class StratumServer:
         job = self.source.get(sub.job_id)
         if job is None or not self.source.is_current_tip(job):
             return self._reject(c, m.id, S.ERR_STALE)
+        sent = None
+        if self.vardiff:
+            with self.lock:
+                sent = list(c.job_targets.get(sub.job_id, ()))
+            if not sent:  # a job this connection was never sent (or one it got too long ago)
+                return self._reject(c, m.id, S.ERR_STALE)
         if sub.header_hash != job.header_hash:
             return self._reject(c, m.id, S.ERR_OTHER, "wrong header hash for the job")
         if not S.nonce_in_extranonce(sub.nonce, c.extranonce):
             return self._reject(c, m.id, S.ERR_OTHER, "nonce outside the extranonce")
         if sub.nonce in job.seen:
             return self._reject(c, m.id, S.ERR_DUPLICATE)
-        target = self.effective_target(job)
         fin = _core.kawpow_hash_no_verify(job.height, job.header_hash, sub.mix_hash, sub.nonce)
-        if int.from_bytes(fin, "big") > target:
+        value = int.from_bytes(fin, "big")
+        # the hardest target that went out with this job to this connection and that the hash meets
+        met = [t for t in (sent or (self.effective_target(job),)) if value <= t]
+        if not met:
             return self._reject(c, m.id, S.ERR_HIGH_HASH)
         job.seen.add(sub.nonce)
-        self.verify_q.put((c, m.id, job, sub, fin))
+        self.verify_q.put((c, m.id, job, sub, fin, share_work(min(met))))
 
     # ------------------------------------------------------------------ the verifier thread
     def _resident(self, epoch: int) -> bool:
@@ -625,6 +783,19 @@ class StratumServer:
         gpu = [b for b in batch if resident[b[2].height // _core.EPOCH_LENGTH]]
         host = [b for b in batch if not resident[b[2].height // _core.EPOCH_LENGTH]]
         results: dict[int, tuple[bytes, bytes]] = {}
+        if host and self.epochs is not None:
+            # an epoch whose DAG is still being built: the light-mode kernel, once its light cache is on the device
+            lit = {e for e, r in resident.items() if not r and self.epochs.mode(e) == "light"}
+            light = [b for b in host if b[2].height // _core.EPOCH_LENGTH in lit]
+            if light:
+                from ..ops import verify as V
+
+                host = [b for b in host if b[2].height // _core.EPOCH_LENGTH not in lit]
+                out = V.gpu_full_hash([b[2].height for b in light], [b[2].header_hash for b in light],
+                                      [b[3].nonce for b in light], device=self.device, mode="light")
+                for b, r in zip(light, out):
+                    results[id(b)] = r
+                self._count("verified_gpu_light", len(light))
         if gpu:
             from ..ops import verify as V
 
@@ -640,13 +811,18 @@ class StratumServer:
                 results[id(b)] = _core.kawpow_hash(ctx, b[2].height, b[2].header_hash, b[3].nonce)
             self._count("verify_batches_host", 1)
             self._count("verified_host", len(host))
-        now = time.time()
+        now = self.clock()
         for b in batch:
-            c, msg_id, job, sub, fin = b
+            c, msg_id, job, sub, fin, work = b
             full_fin, full_mix = results[id(b)]
             if bytes(full_mix) != sub.mix_hash or bytes(full_fin) != fin:
                 log.log_printf(f"stratum: connection {c.id} ({c.addr[0]}) sent a wrong mix for nonce {sub.nonce:016x}; closed")
+                # counted before the peer can see the close: its next connection already meets the ban
+                banned = self.bans is not None and self.bans.strike(c.addr[0], now)
                 self._reject(c, msg_id, S.ERR_OTHER, "wrong mix", close=True)
+                if banned:
+                    log.log_printf(f"stratum: {c.addr[0]} sent {BAN_STRIKES} wrong mixes within {int(BAN_WINDOW_S)} s; "
+                                   f"refused for {int(self.bans.ban_s)} s")
                 continue
             if not self.source.is_current_tip(job):  # the tip moved while the share waited for its hash
                 self._reject(c, msg_id, S.ERR_STALE)
@@ -654,7 +830,8 @@ class StratumServer:
             with self.lock:
                 c.accepted += 1
                 c.last_share = now
-                c.accept_times.append(now)
+                c.accept_times.append((now, work))
+                c.shares_since += 1
                 self.stats["accepted"] += 1
             if int.from_bytes(fin, "big") <= job.block_target and self.source.is_current_tip(job):
                 try:
@@ -670,19 +847,18 @@ class StratumServer:
             self._send(c, S.response(msg_id, True))
 
     # ------------------------------------------------------------------ getstratuminfo
-    def _info_target(self) -> int:
-        job = self.source.current()
-        return (self.effective_target(job) if job is not None else self.share_target) or (1 << 256) - 1
-
     def info(self) -> dict:
         job = self.source.current()
-        now = time.time()
+        now = self.clock()
         algo = getattr(self.source, "algo", "kawpow")
         target = self.effective_target(job) if job is not None else self.share_target
         with self.lock:
-            conns = [c.info(target or (1 << 256) - 1, now) for c in self.conns.values()]
+            conns = [c.info(now) for c in self.conns.values()]
             recent = list(self.recent)
             stats = dict(self.stats)
+        stats["vardiff"] = self.vardiff
+        if self.epochs is not None:
+            stats.update(self.epochs.info())
         out = {"enabled": True, "port": self.port, "serving": job is not None, "algo": algo,
                "height": job.height if job is not None else None,
                "job": {"id": job.job_id, "header_hash": job.header_hash.hex(), "age": round(now - job.created, 3)}

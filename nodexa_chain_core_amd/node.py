@@ -475,15 +475,41 @@ class Node:
 
     def _start_stratum(self, a: ArgsManager) -> None:
         """-stratumport: the Stratum server (miner/stratum_server.py) on -stratumbind, jobs paying
-        -miningaddress, shares at -stratumsharebits, full share hashes on the miner's GPU when its
-        DAG is resident there."""
+        -miningaddress, shares at -stratumsharebits (per connection with -stratumvardiff), full share
+        hashes on the GPU against the miner's resident DAG or, with -stratumgpuverify=1, one the server
+        builds itself; -stratumbantime refuses addresses that keep sending wrong mixes."""
         from .miner.stratum_server import ChainJobSource, StratumServer
 
+        share_bits = a.get_int("stratumsharebits", 0)
+        vardiff = a.get_int("stratumvardiff", 0)
+        if vardiff < 0:
+            raise SystemExit(f"Error: invalid -stratumvardiff={vardiff} (shares per minute and connection, 0 = off)")
+        if vardiff and not 0 < share_bits <= 255:
+            raise SystemExit("Error: -stratumvardiff needs -stratumsharebits above 0: every connection starts there, "
+                             "and it is the easiest target vardiff gives")
+        gpu_verify = a.get("stratumgpuverify", "0")
+        if gpu_verify not in ("0", "1"):
+            raise SystemExit(f"Error: invalid -stratumgpuverify={gpu_verify} (expected 0 or 1)")
+        ban_s = a.get_int("stratumbantime", 0)
+        if ban_s < 0:
+            raise SystemExit(f"Error: invalid -stratumbantime={ban_s} (seconds, 0 = off)")
+        device = self.gpus[0] if self.gpus else None
+        owner = None
+        if gpu_verify == "1" and device is not None:
+            from .miner.stratum_epochs import EpochOwner, device_builder
+
+            def miner_pending(epoch: int) -> bool:  # the in-process miner's own prebuild of that epoch
+                dev = getattr(getattr(self.miner, "service", None), "dev", None)
+                pending = getattr(dev, "pending_epochs", None)
+                return pending is not None and getattr(dev, "device", None) == device and epoch in pending()
+
+            owner = EpochOwner(device, device_builder(device, a.get("dagcheck", "1") != "0"),
+                               foreign_pending=miner_pending)
         source = ChainJobSource(self.state, self.mining_script, refresh_s=self.miner.leader.refresh_s)
         self.stratum = StratumServer(source, host=a.get("stratumbind", "127.0.0.1"), port=a.get_int("stratumport", 0),
-                                     share_bits=a.get_int("stratumsharebits", 0), password=a.get("stratumpassword"),
-                                     max_connections=a.get_int("stratummaxconn", 64),
-                                     device=self.gpus[0] if self.gpus else None)
+                                     share_bits=share_bits, password=a.get("stratumpassword"),
+                                     max_connections=a.get_int("stratummaxconn", 64), device=device,
+                                     vardiff=vardiff, ban_s=float(ban_s), epoch_owner=owner)
         try:
             self.stratum.start()
         except OSError as e:

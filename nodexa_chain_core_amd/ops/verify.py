@@ -91,15 +91,37 @@ def prefetch_contexts(epochs, device: int) -> None:
 
 
 def _light_epoch(epoch: int, device: int) -> DeviceEpoch:
+    # the Stratum server's build thread (miner/stratum_epochs.py) uploads light caches while its
+    # verifier hashes against them: the table is changed under a lock of its own, the upload (and
+    # the host's light-cache build behind it) runs outside it
     key = (device, epoch)
-    e = _light.get(key)
+    with _light_lock:
+        e = _light.get(key)
     if e is None:
-        if len(_light) >= 8:
-            _light.pop(next(iter(_light)))
         with torch.cuda.device(device):
             e = DeviceEpoch(epoch, device=device, light_only=True)
-        _light[key] = e
+        with _light_lock:
+            have = _light.get(key)
+            if have is not None:
+                return have
+            if len(_light) >= 8:
+                _light.pop(next(iter(_light)))
+            _light[key] = e
     return e
+
+
+_light_lock = threading.Lock()
+light_epoch = _light_epoch
+
+
+def drop_resident(device: int, epoch: int, e: DeviceEpoch) -> bool:
+    """Take `e` out of the registry if it is still what is registered for (device, epoch): the
+    component that built a DAG drops its own, never one that another component shared since."""
+    with _epochs_lock:
+        if _epochs.get((device, epoch)) is e:
+            _epochs.pop((device, epoch))
+            return True
+    return False
 
 
 def register_resident(epoch_dev: DeviceEpoch) -> None:

@@ -784,12 +784,20 @@ def register(table, node) -> None:  # noqa: C901 — one table, like the referen
           "verified_gpu": n, "verified_host": n, "verify_batches_gpu": n, "verify_batches_host": n,
                                        (numeric) shares fully hashed on the GPU's resident DAG / on the host, and the batches
           "accepted": n, "rejected": n, ...      (numeric) server-wide counters
+          "vardiff": n,                (numeric) -stratumvardiff: wanted shares per minute and connection, 0 = one target for all
+          "verified_gpu_light": n, "dag_builds": n, "dag_build_failures": n, "dag_last_build_ms": x, "epochs_resident": [n, ...],
+                                       only with -stratumgpuverify=1 and a GPU: shares hashed by the light-mode kernel while a
+                                       DAG was being built, the DAGs the server built for share checks, and the epochs whose
+                                       DAG is resident on the device now (the miner's included)
           "connections": [             one entry per live connection
             {"id", "address", "agent", "user", "extranonce", "connected" (seconds), "accepted",
-             "rejected" ({"code": n}), "last_share" (unix time), "hashrate" (accepted shares x 2^256 /
-             (share target + 1) over the connection's lifetime or the last 10 minutes, whichever is shorter)}
+             "rejected" ({"code": n}), "last_share" (unix time), "hashrate" (the work of the accepted shares, each
+             2^256 / (its target + 1), over the connection's lifetime or the last 10 minutes, whichever is shorter),
+             "share_bits" (the connection's current share bits), "retargets" (vardiff changes of them),
+             "shares_per_minute" (accepted, over the same time as the hashrate)}
           ],
-          "recent_connections": [...]  the last 8 closed connections as they ended, with "closed" (unix time)
+          "recent_connections": [...]  the last 8 closed connections as they ended, with "closed" (unix time); a connection
+                                       refused under -stratumbantime appears as {"address", "refused", "banned_until", "closed"}
         }
         """
         srv = getattr(node, "stratum", None)

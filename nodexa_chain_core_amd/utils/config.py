@@ -32,7 +32,13 @@ Stratum server of the node (miner/stratum_server.py; needs -miningaddress, KawPo
 -stratumport=<port> (off without it), -stratumbind=<addr> (default 127.0.0.1), -stratumsharebits=<n>
 (share target 2^(256-n) - 1 as -minertargetbits; the effective target is the easier of it and the
 block target), -stratumpassword=<pw> (mining.authorize must present it), -stratummaxconn=<n>
-(default 64; further connections are refused). nodexa-miner: -stratum=host:port (repeatable, tried
+(default 64; further connections are refused), -stratumvardiff=<shares per minute> (default 0 =
+off: a share target per connection, from -stratumsharebits upwards, steered to that rate; needs
+-stratumsharebits above 0), -stratumgpuverify=0|1 (default 0: with 1 and a GPU the server builds
+the DAG of the served epoch itself when the miner has none there, and the next epoch's 120 blocks
+ahead, so that shares are checked on the GPU; -dagcheck applies), -stratumbantime=<seconds>
+(default 0 = off: an address closed for a wrong mix 3 times within 10 minutes is refused that
+long). nodexa-miner: -stratum=host:port (repeatable, tried
 in order), -stratumuser=, -stratumpass= (default x).
 """
 from __future__ import annotations

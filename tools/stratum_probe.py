@@ -12,6 +12,19 @@ that moved the tip would measure itself.
 
     python tools/stratum_probe.py --gpu 0 [--changes 20] [--window 33554432] [--kawpowjit wait|auto|off]
                                   [--order stratum,getblocktemplate] [--markdown]
+
+`--mode verify` needs no miner and no node: it measures the server's share checks alone. Two
+servers with a `StaticJobSource` in this one process, one as a node without -stratumgpuverify and
+without a miner sees it (no device: every share on the host) and one with -stratumgpuverify=1 on
+`--gpu`, are sent the same pipelined `mining.submit` lines in turn (0, 1, 0, 1, ...): batches of
+`--batches` submits written in one piece, at `--epochs`, `--repeats` timed rounds after `--warmups`
+untimed ones, median (min-max) of submits answered per second. Every nonce is a share (the jobs'
+block target is 2^256 - 1), its mix computed beforehand on the host. Then, per epoch, the time from
+the start of a fresh -stratumgpuverify=1 server (no DAG resident; the host's light cache is in the
+native cache after the warm-ups) until the first share it answers was hashed on its DAG, one share
+being submitted after the other meanwhile.
+
+    python tools/stratum_probe.py --mode verify --gpu 0 [--epochs 0,384] [--batches 1,16,256] [--markdown]
 """
 from __future__ import annotations
 
@@ -108,8 +121,128 @@ def measure(node, addr, leader, dev, window: int, changes: int, on_stop=None) ->
     return out, step_ms
 
 
+def _minmax(v: list[float], nd: int = 1) -> dict:
+    return {"median": round(statistics.median(v), nd), "min": round(min(v), nd), "max": round(max(v), nd),
+            "samples": [round(x, nd) for x in v]}
+
+
+def verify_mode(a) -> int:
+    import socket
+
+    from nodexa_chain_core_amd import _core
+    from nodexa_chain_core_amd.miner import stratum as S
+    from nodexa_chain_core_amd.miner.stratum_server import ServerJob, StaticJobSource, StratumServer
+
+    epochs = [int(x) for x in a.epochs.split(",")]
+    batches = [int(x) for x in a.batches.split(",")]
+    hh = _core.sha256d(b"stratum probe header")
+    top = (1 << 256) - 1
+    seq = [0]
+
+    def server(flag: int):
+        src = StaticJobSource()
+        srv = StratumServer(src, device=a.gpu if flag else None, gpu_verify=bool(flag)).start()
+        sock = socket.create_connection(("127.0.0.1", srv.port), timeout=120)
+        f = sock.makefile("rb")
+        sock.sendall(S.subscribe(1, "probe") + S.authorize(2, "probe", "x"))
+        f.readline(), f.readline()
+        return srv, src, sock, f
+
+    def new_job(src, f, height: int) -> str:
+        seq[0] += 1
+        job = ServerJob("p%x" % seq[0], hh, height, top, 0x207FFFFF, True, "tip")
+        src.push(job)
+        while True:  # set_target (first job only), then the notify
+            if S.decode(f.readline()).method == "mining.notify":
+                return job.job_id
+
+    def lines(job_id: str, shares) -> bytes:
+        return b"".join(S.submit(10 + i, S.Submit("probe", job_id, n, hh, mix)) for i, (n, mix) in enumerate(shares))
+
+    def answered(f, n: int) -> None:
+        for _ in range(n):
+            m = S.decode(f.readline())
+            if m.result is not True:
+                raise RuntimeError(f"a share was refused: {m.error}")
+
+    out = {"mode": "verify", "device": f"gpu{a.gpu}", "repeats": a.repeats, "warmups": a.warmups, "rate": {}, "first_dag_share_ms": {}}
+    for epoch in epochs:
+        height = epoch * _core.EPOCH_LENGTH + 1
+        ctx = _core.get_epoch_context(epoch)
+        shares = [(n, _core.kawpow_hash(ctx, height, hh, n)[1]) for n in range(1 << 48, (1 << 48) + max(batches))]
+        pair = {flag: server(flag) for flag in (0, 1)}
+        try:
+            job_id = new_job(pair[1][1], pair[1][3], height)
+            deadline = time.monotonic() + 300
+            while not (pair[1][0].epochs.ready(epoch) and pair[1][0].epochs.idle()):
+                if time.monotonic() > deadline:
+                    raise RuntimeError(f"no DAG of epoch {epoch}: {pair[1][0].info()}")
+                time.sleep(0.01)
+            for n in batches:
+                rates = {0: [], 1: []}
+                for rep in range(a.warmups + a.repeats):
+                    for flag in (0, 1):
+                        srv, src, sock, f = pair[flag]
+                        job_id = new_job(src, f, height)
+                        data = lines(job_id, shares[:n])
+                        before = dict(srv.stats)
+                        t0 = time.perf_counter()
+                        sock.sendall(data)
+                        answered(f, n)
+                        dt = time.perf_counter() - t0
+                        key = "verified_gpu" if flag else "verified_host"
+                        if srv.stats[key] - before[key] != n:
+                            raise RuntimeError(f"flag {flag}: the shares were not all hashed where they should be: {srv.stats}")
+                        if rep >= a.warmups:
+                            rates[flag].append(n / dt)
+                out["rate"][f"epoch{epoch}_batch{n}"] = {f"gpuverify{flag}": _minmax(v) for flag, v in rates.items()}
+            out.setdefault("dag_build_ms", {})[f"epoch{epoch}"] = pair[1][0].info()["dag_last_build_ms"]
+        finally:
+            for srv, _src, sock, _f in pair.values():
+                sock.close()
+                srv.stop()
+        first, before_dag = [], []
+        for rep in range(a.warmups + a.repeats):
+            t0 = time.perf_counter()
+            srv, src, sock, f = server(1)
+            try:
+                job_id = new_job(src, f, height)
+                k = 0
+                while srv.stats["verified_gpu"] == 0:
+                    sock.sendall(lines(job_id, shares[k:k + 1]))
+                    answered(f, 1)
+                    k += 1
+                    if k >= len(shares):
+                        job_id, k = new_job(src, f, height), 0
+                dt = (time.perf_counter() - t0) * 1e3
+                if rep >= a.warmups:
+                    first.append(dt)
+                    before_dag.append({"host": srv.stats["verified_host"], "light": srv.stats["verified_gpu_light"]})
+            finally:
+                sock.close()
+                srv.stop()
+        out["first_dag_share_ms"][f"epoch{epoch}"] = dict(_minmax(first), shares_before=before_dag)
+    if a.markdown:
+        print("| epoch | submits in one piece | -stratumgpuverify=0: shares/s median (min-max) | =1: shares/s median (min-max) |\n|---|---|---|---|")
+        for key, v in out["rate"].items():
+            e, n = key.split("_")
+            c = [f"{v[f'gpuverify{i}']['median']} ({v[f'gpuverify{i}']['min']}-{v[f'gpuverify{i}']['max']})" for i in (0, 1)]
+            print(f"| {e[5:]} | {n[5:]} | {c[0]} | {c[1]} |")
+        print("\n| epoch | server start to first DAG-verified share, ms median (min-max) |\n|---|---|")
+        for key, v in out["first_dag_share_ms"].items():
+            print(f"| {key[5:]} | {v['median']} ({v['min']}-{v['max']}) |")
+        print()
+    print(json.dumps(out))
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", default="tip", choices=("tip", "verify"))
+    ap.add_argument("--epochs", default="0,384")
+    ap.add_argument("--batches", default="1,16,256")
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--warmups", type=int, default=2)
     ap.add_argument("--gpu", type=int, default=None)
     ap.add_argument("--cpu", action="store_true")
     ap.add_argument("--changes", type=int, default=20)
@@ -120,6 +253,10 @@ def main() -> int:
                          "ProgPoW period, also waits for that period's kernel")
     ap.add_argument("--order", default="stratum,getblocktemplate", help="which path is measured first")
     a = ap.parse_args()
+    if a.mode == "verify":
+        if a.gpu is None:
+            ap.error("--mode verify needs --gpu")
+        return verify_mode(a)
     cpu = a.cpu or a.gpu is None
     window = a.window or (8 if cpu else 1 << 25)
 
