@@ -1,6 +1,7 @@
-"""Equihash(200,9) CPU golden model (no reference implementation exists:
-parity unpinned against the reference; checked against the public spec's
-rules, RFC 7693 BLAKE2b and self-consistency)."""
+"""Equihash(200,9) CPU golden model: RFC 7693 BLAKE2b, parameters, packing and
+solver/verifier self-consistency. The reference has no Equihash to compare
+with; the verifier's rules are pinned to an independent oracle
+(tests/equihash_oracle.py) in tests/test_equihash_oracle.py."""
 import pytest
 
 

@@ -86,8 +86,22 @@ def test_gpu_batch_verify_matches_cpu(core, solver):
                 batch_in.append(inp)
                 batch_sol.append(core.equihash_pack(p, bad))
                 expect.append(bool(core.equihash_verify(p, inp, bad)[0]))
+    # valid solutions no solver of the project produced (tests/data/equihash_adversarial.json)
+    import equihash_oracle
+
+    mined = [c for c in equihash_oracle.load_fixtures() if c.cls == "valid"]
+    for c in mined:
+        if len(c.inp) == 112:
+            batch_in.append(c.inp)
+            batch_sol.append(c.packed)
+            expect.append(True)
+    assert sum(len(c.inp) == 112 for c in mined) >= 2
     assert any(expect) and not all(expect)
     assert verify_solutions(batch_in, batch_sol, device=0) == expect
+    for c in mined:  # one input length per batch: the other input lengths on their own
+        if len(c.inp) != 112:
+            bad = c.indices[256:] + c.indices[:256]
+            assert verify_solutions([c.inp, c.inp], [c.packed, core.equihash_pack(p, bad)], device=0) == [True, False]
 
 
 def test_gpu_repeatable(solver):
