@@ -284,7 +284,16 @@ class ChainState:
         self.sig_stats = {"gpu_batches": 0, "gpu_sigs": 0, "host_rechecks": 0, "gpu_sighashes": 0,
                           "host_sighashes": 0, "gpu_sighashes_v0": 0, "gpu_sighashes_partial": 0,
                           "gpu_windows": 0, "window_blocks": 0, "window_sigs": 0, "window_rollbacks": 0,
-                          "gpu_multisig_groups": 0, "gpu_multisig_entries": 0}
+                          "gpu_multisig_groups": 0, "gpu_multisig_entries": 0,
+                          "script_cache_txs": 0, "script_cache_blocks": 0}
+        # -scriptcache=0|1: the script-execution cache (csrc/chain/scriptcache.hpp). 1: a transaction
+        # that passes accept_to_mempool is run once more under the block flags and remembered by
+        # (wtxid, flags); connect_block then skips every script of a remembered transaction, on the
+        # host path and in the GPU batch alike, and _connect_final erases the entries a block hit.
+        # script_cache_txs / script_cache_blocks (above): transactions skipped that way in blocks made
+        # final, and the blocks that had at least one. 0 (the default; the reference has the cache
+        # always on): no path differs and the cache is never touched
+        self.script_cache = False
         # -gpusigwindow=<signatures>: with the GPU batch, _activate connects consecutive blocks
         # speculatively and verifies their signatures in one device pass of about this many (0: off,
         # every block on its own)
@@ -1286,18 +1295,22 @@ class ChainState:
 
         gpu_hash = gpu and self.gpu_sighash  # only with the GPU batch: the host path hashes as it verifies
 
+        # -scriptcache: transactions the mempool verified under these flags leave nothing to check or
+        # defer. The lookup never erases, so the host re-run below and a window's roll-back hit again
+        cached = bool(self.script_cache)
+
         def connect(defer: bool):
             if defer and self.gpu_multisig:
                 return _core.connect_block(block, height, self.coins, check_scripts, defer, mtp_at, mtp_prev, flags,
                                            par, self.assets, aflags, idx.hash, defer_sighash=bool(gpu_hash),
                                            defer_all_forms=bool(gpu_hash) and self.gpu_sighash_forms == "all",
-                                           defer_multisig=True)
+                                           defer_multisig=True, script_cache=cached)
             if defer and gpu_hash:
                 return _core.connect_block(block, height, self.coins, check_scripts, defer, mtp_at, mtp_prev, flags,
                                            par, self.assets, aflags, idx.hash, defer_sighash=True,
-                                           defer_all_forms=self.gpu_sighash_forms == "all")
+                                           defer_all_forms=self.gpu_sighash_forms == "all", script_cache=cached)
             return _core.connect_block(block, height, self.coins, check_scripts, defer, mtp_at, mtp_prev, flags, par,
-                                       self.assets, aflags, idx.hash)
+                                       self.assets, aflags, idx.hash, script_cache=cached)
 
         res, undo = connect(gpu)
         if gpu and not res.ok and "script-verify" in res.reject:
@@ -1363,6 +1376,13 @@ class ChainState:
         if aundo:  # beside the block's file too, so pruning a blk file drops its asset undo with it
             self.asset_undo.write(idx.hash, idx.prev_hash, aundo, file=bpos.file if bpos is not None else None)
         self.coins.best_block = idx.hash
+        hits = res.script_cache_txs
+        if hits:
+            # the reference erases a script-cache entry when ConnectBlock hits it; here only the
+            # final half does, so a block that is re-run or rolled back finds its entries again
+            res.script_cache_erase()  # by the keys the lookup used
+            self.sig_stats["script_cache_txs"] += len(hits)
+            self.sig_stats["script_cache_blocks"] += 1
         self.record_confirmations(block, height)
         self._emit("connect_tip", block, idx, undo)
         self._since_flush += 1
@@ -1820,6 +1840,21 @@ class ChainState:
                                                  _core.BLOCK_SCRIPT_VERIFY_FLAGS, raw, k, value)
                     kind = "non-mandatory-script-verify-flag" if ok2 else "mandatory-script-verify-flag-failed"
                     return False, f"{kind} ({err})", fee
+            if self.script_cache:
+                # CheckInputsFromMempoolAndCache: once more under the flags connect_block will use, so
+                # that the block that confirms this transaction can skip its scripts altogether
+                # (scriptExecutionCache, src/validation.cpp:9231-9335). The signature cache is in
+                # store mode: the ECDSA work hits the entries the loop above just wrote
+                for k, (value, spk) in enumerate(coins):
+                    vin = tx.vin[k]
+                    ok, err = _core.verify_script(vin.script_sig, spk, list(vin.witness),
+                                                  _core.BLOCK_SCRIPT_VERIFY_FLAGS, raw, k, value, 1)
+                    if not ok:  # passed the standard flags, fails the mandatory ones: never expected
+                        log.log_printf(f"BUG! {_core.u256_hex(txid)} passes the standard script flags "
+                                       f"and fails the block's: {err}")
+                        return False, f"mandatory-script-verify-flag-failed ({err})", fee
+                if not test_only:
+                    _core.scriptcache_insert(tx.wtxid(), _core.BLOCK_SCRIPT_VERIFY_FLAGS)
             if not test_only:
                 # BIP125: the replaced transactions and their descendants leave (kept aside for
                 # compact-block reconstruction: vExtraTxnForCompact)

@@ -10,6 +10,7 @@
 #include "../chain/coins.hpp"
 #include "../chain/indexes.hpp"
 #include "../chain/interpreter.hpp"
+#include "../chain/scriptcache.hpp"
 #include "../chain/sigcache.hpp"
 #include "../chain/sighash.hpp"
 #include "../chain/params.hpp"
@@ -237,6 +238,33 @@ void bind_script(py::module_& m) {
         d["evictions"] = s.evictions;
         return d;
     });
+    // ---- the script-execution cache (-scriptcache, chain/scriptcache.hpp)
+    auto wtxid_of = [](const py::bytes& wtxid) {
+        const std::string w = wtxid;
+        if (w.size() != 32) throw std::invalid_argument("wtxid: 32 bytes");
+        return Uint256::from_bytes(reinterpret_cast<const u8*>(w.data()));
+    };
+    m.def("scriptcache_set_max_bytes", [](size_t b) { ScriptCache::instance().set_max_bytes(b); },
+          "half of -maxsigcachesize (bytes of 32-byte entries)");
+    m.def("scriptcache_clear", [] { ScriptCache::instance().clear(); });
+    m.def("scriptcache_stats", [] {
+        const ScriptCache::Stats s = ScriptCache::instance().stats();
+        py::dict d;
+        d["entries"] = s.entries;
+        d["max_entries"] = s.max_entries;
+        d["hits"] = s.hits;
+        d["misses"] = s.misses;
+        d["inserts"] = s.inserts;
+        d["erases"] = s.erases;
+        d["evictions"] = s.evictions;
+        return d;
+    });
+    m.def("scriptcache_contains", [wtxid_of](const py::bytes& wtxid, u32 flags) {
+        return ScriptCache::instance().contains(wtxid_of(wtxid), flags);
+    }, py::arg("wtxid"), py::arg("flags"), "whether every script of the transaction passed under these flags");
+    m.def("scriptcache_insert", [wtxid_of](const py::bytes& wtxid, u32 flags) {
+        ScriptCache::instance().insert(wtxid_of(wtxid), flags);
+    }, py::arg("wtxid"), py::arg("flags"));
     m.def("eval_script", [](const std::vector<py::bytes>& stack, const py::bytes& script, u32 flags) {
         std::vector<Bytes> st = stack_of(stack);
         ScriptError err = ScriptError::UNKNOWN_ERROR;
@@ -365,6 +393,14 @@ void bind_script(py::module_& m) {
         .def_readonly("fees", &ConnectResult::fees)
         .def_readonly("sigop_cost", &ConnectResult::sigop_cost)
         .def_readonly("sig_at", &ConnectResult::sig_at)
+        .def_readonly("script_cache_txs", &ConnectResult::script_cache_txs,
+                      "with script_cache: block index of every transaction the script-execution cache answered for")
+        .def("script_cache_erase", [](const ConnectResult& r) {
+            size_t n = 0;
+            for (const Uint256& w : r.script_cache_wtxids) n += ScriptCache::instance().erase(w, r.script_cache_flags);
+            return n;
+        }, "erase the script-cache entries of script_cache_txs, under the flags they were looked up with (the block "
+           "is final) -> how many were still there")
         .def_property_readonly("asset_undo", [](const ConnectResult& r) { return pyb(r.asset_undo); })
         .def_property_readonly("num_sigs", [](const ConnectResult& r) { return r.sigs.size(); })
         .def_property_readonly("num_device_hashes", [](const ConnectResult& r) {
@@ -614,8 +650,9 @@ void bind_script(py::module_& m) {
     m.def("connect_block", [](const Block& block, int height, CoinsView& view, bool check_scripts, bool defer_sigs,
                               py::object mtp_at, int64_t block_mtp, u32 flags, int threads, assets::State* asset_state,
                               const assets::Flags& asset_flags, const py::bytes& block_hash, bool sigcache,
-                              bool defer_sighash, bool defer_all_forms, bool defer_multisig) {
+                              bool defer_sighash, bool defer_all_forms, bool defer_multisig, bool script_cache) {
         ConnectOptions opt;
+        opt.script_cache = script_cache;
         opt.defer_sighash = defer_sighash;
         opt.defer_all_forms = defer_all_forms;
         opt.defer_multisig = defer_multisig;
@@ -648,7 +685,11 @@ void bind_script(py::module_& m) {
        py::arg("flags") = kBlockScriptFlags, py::arg("threads") = 1, py::arg("assets") = nullptr,
        py::arg("asset_flags") = assets::Flags{}, py::arg("block_hash") = py::bytes(), py::arg("sigcache") = true,
        py::arg("defer_sighash") = false, py::arg("defer_all_forms") = false, py::arg("defer_multisig") = false,
+       py::arg("script_cache") = false,
        "ConnectBlock against the view -> (ConnectResult, serialized CBlockUndo); the view is unchanged on failure. "
+       "script_cache: a transaction whose (wtxid, flags) is in the script-execution cache gets no script check, no "
+       "deferred signature and no template or forms entry; its block index is listed in "
+       "ConnectResult.script_cache_txs and nothing is erased here. "
        "defer_multisig (with defer_sigs only): a CHECKMULTISIG whose outcome depends on its pair verdicts alone leaves "
        "every candidate (signature, key) pair among the deferred signatures and a record in ConnectResult.sig_groups; "
        "those entries neither consult nor erase the signature cache. "
@@ -656,7 +697,9 @@ void bind_script(py::module_& m) {
        "(ConnectResult.sighash_pack); those signatures are not looked up in the signature cache, whose key is the "
        "message, so their entries age out of the bounded cache instead of being erased on use. defer_all_forms (with "
        "defer_sighash only): every form of both signature versions is left to the batch "
-       "(ConnectResult.sighash_pack_var), and the same holds for the witness signatures' cache entries");
+       "(ConnectResult.sighash_pack_var), and the same holds for the witness signatures' cache entries. With "
+       "-scriptcache=1 (script_cache) a transaction the mempool verified is skipped as a whole, which is what spares "
+       "those signatures");
     m.def("disconnect_block", [](const Block& block, const py::bytes& undo, CoinsView& view, assets::State* st,
                                  const py::bytes& asset_undo) {
         const Bytes au = bytes_of(asset_undo);

@@ -17,6 +17,7 @@
 
 #include "../crypto/secp256k1.hpp"
 #include "../crypto/sha256.hpp"
+#include "scriptcache.hpp"
 
 namespace nodexa {
 
@@ -623,6 +624,8 @@ ConnectResult connect_block(const Block& block, int height, CoinsView& view, con
         res.sig_groups.clear();
         res.templates.clear();
         res.forms.clear();
+        res.script_cache_txs.clear();
+        res.script_cache_wtxids.clear();
         return res;
     };
     struct Check {
@@ -639,6 +642,7 @@ ConnectResult connect_block(const Block& block, int height, CoinsView& view, con
     const bool defer_sighash = opt.defer_sigs && opt.defer_sighash;
     const bool all_forms = defer_sighash && opt.defer_all_forms;
     res.all_forms = all_forms;
+    res.script_cache_flags = opt.script_flags;
     if (all_forms) res.forms.resize(block.vtx.size());
     else if (defer_sighash) res.templates.resize(block.vtx.size());
     for (size_t t = 0; t < block.vtx.size(); ++t) {
@@ -696,7 +700,18 @@ ConnectResult connect_block(const Block& block, int height, CoinsView& view, con
         }
         res.sigop_cost += tx_sigop_cost(tx, spent, opt.script_flags);
         if (res.sigop_cost > kMaxBlockSigopsCost) return fail("bad-blk-sigops", 100);
-        if (!tx.is_coinbase() && opt.check_scripts) {
+        // the script-execution cache: every script of this transaction passed under these flags when
+        // it entered the mempool (the key is the witness hash), so it takes no part in the checks
+        bool cached = false;
+        if (!tx.is_coinbase() && opt.check_scripts && opt.script_cache) {
+            const Uint256 wtxid = tx.wtxid();
+            cached = ScriptCache::instance().contains(wtxid, opt.script_flags);
+            if (cached) {
+                res.script_cache_txs.push_back(u32(t));
+                res.script_cache_wtxids.push_back(wtxid);
+            }
+        }
+        if (!tx.is_coinbase() && opt.check_scripts && !cached) {
             if (all_forms) res.forms[t] = std::make_shared<const SighashTxForms>(tx);  // holds the midstates too
             else caches[t] = std::make_unique<PrecomputedTx>(tx);
             if (defer_sighash && !all_forms) res.templates[t] = std::make_shared<const SighashTemplate>(tx);

@@ -135,20 +135,29 @@ struct ConnectOptions {
     // With defer_sigs: also leave the legacy SIGHASH_ALL-form message hashes to the batch
     // (interpreter.hpp sighash_all_form; chain/sighash.hpp packs them for the GPU). Those
     // signatures are not looked up in the signature cache, whose key is the message: their entries
-    // age out of the bounded cache instead of being erased on use.
+    // age out of the bounded cache instead of being erased on use. With -scriptcache=1 a transaction
+    // the mempool verified is skipped as a whole (script_cache below), which is what spares them.
     bool defer_sighash = false;
     // With defer_sighash: leave every form of both signature versions to the batch (NONE, SINGLE,
     // ANYONECANPAY and witness v0 too; chain/sighash.hpp pack_sighash_var). None of the deferred
-    // signatures, witness ones included, is looked up in the signature cache.
+    // signatures, witness ones included, is looked up in the signature cache. With -scriptcache=1 a
+    // transaction the mempool verified is skipped as a whole, which is what spares them.
     bool defer_all_forms = false;
     // With defer_sigs: a CHECKMULTISIG whose outcome depends on its pair verdicts alone records
     // every candidate (signature, key) pair and a group record (interpreter.hpp SigGroupRec), and
     // the batch runs the pairing walk (chain/sighash.hpp sig_group_resolve_model), so an input
     // signed by any subset of its keys needs no host re-check. Group entries neither consult nor
     // erase the signature cache, whatever their hash's origin: like the deferred hashes above,
-    // their cache entries age out instead of being erased on use.
+    // their cache entries age out instead of being erased on use. With -scriptcache=1 a transaction
+    // the mempool verified is skipped as a whole, which is what spares them.
     bool defer_multisig = false;
     bool sigcache = true;      // skip (and drop) signatures the mempool already verified (sigcache.hpp)
+    // -scriptcache=1: a non-coinbase transaction whose (wtxid, script_flags) is in the script-execution
+    // cache (scriptcache.hpp) gets no script check at all: no check is pushed, and no template, forms
+    // or precomputed data is built for it. Everything else still runs for it (inputs present and
+    // mature, amounts, sequence locks, sigop cost, BIP30, asset rules, undo). connect_block only
+    // looks up; the caller erases the entries of ConnectResult.script_cache_txs once the block is final.
+    bool script_cache = false;
     bool sequence_locks = true;
     // median time past of the block at `height` of this block's chain (BIP68 time locks)
     std::function<int64_t(int)> mtp_at;
@@ -174,6 +183,11 @@ struct ConnectResult {
     // with defer_multisig: the CHECKMULTISIG groups among sigs, ascending and disjoint
     std::vector<SigGroupRec> sig_groups;
     Bytes asset_undo;                          // the asset journal of the block (with opt.assets)
+    // with script_cache: block index of every transaction the script-execution cache answered for;
+    // such a transaction has no entry in sigs / sig_at / sig_groups and a null templates[t] / forms[t]
+    std::vector<u32> script_cache_txs;
+    std::vector<Uint256> script_cache_wtxids;  // their witness hashes, in the same order
+    u32 script_cache_flags = 0;                // the flags they were looked up under: what the caller erases by
     // with defer_sighash: the template of every transaction that has a deferred hash, by block index
     std::vector<std::shared_ptr<const SighashTemplate>> templates;
     // with defer_all_forms instead: what the batch needs of every checked transaction, by block index

@@ -315,6 +315,13 @@ class Node:
                 log.log_printf(f"-{flag} has no effect in this build")
         # -maxsigcachesize (MiB, src/script/sigcache.cpp InitSignatureCache): bounded by its 32-byte entries
         _core.sigcache_set_max_bytes(max(0, a.get_int("maxsigcachesize", 32)) << 20)
+        # -scriptcache=0|1: the script-execution cache (InitScriptExecutionCache, src/init.cpp:1346): a
+        # transaction verified at mempool acceptance is skipped as a whole in the block that confirms
+        # it, with or without the GPU batch. It is bounded by half of -maxsigcachesize, the reference's
+        # split; the signature cache keeps the whole figure here, where the reference halves it too.
+        # The reference has this cache always on; here the default is 0
+        _core.scriptcache_set_max_bytes((max(0, a.get_int("maxsigcachesize", 32)) << 20) // 2)
+        self.state.script_cache = a.get_int("scriptcache", 0) > 0
         par = int(a.get("par", "0"))  # -par: 0 = one per core (as the reference), <0 leaves that many cores free
         cores = os.cpu_count() or 1
         self.state.script_threads = max(1, min(16, cores + par if par <= 0 else par))
@@ -960,7 +967,7 @@ class Node:
         for g in out:
             g["intensity"] = svc.window
             g["ranks"] = svc.world_size
-        if out:  # the node's own entry: block validation's GPU batches (-gpusigs, -gpusighash, -gpusigwindow)
+        if out:  # the node's own entry: block validation's GPU batches (-gpusigs, -gpusighash, -gpusigwindow, -scriptcache)
             out[0]["block_sigs"] = dict(self.state.sig_stats)
         if out and self.gpus:
             try:

@@ -28,6 +28,13 @@ cache; needs -dagcheck=1. The flags reach every rank of the miner world through 
 reference: up to min(8, n) of them outbound, and n less the outbound slots and one more for
 inbound peers; at that limit a new inbound peer takes the place of an evictable one or is refused.
 
+-scriptcache=0|1 (default 0; the reference has this cache always on): the script-execution cache. A
+transaction that passes mempool acceptance is run once more under the block's script flags and
+remembered by (witness hash, flags); the block that confirms it then runs none of its scripts, on
+the host path and in the GPU batch (-gpusigs, -gpusighash, -gpumultisig, -gpusigwindow) alike. The
+cache takes half of -maxsigcachesize (default 32 MiB, so 16 MiB), the reference's split; the
+signature cache keeps the whole figure here. -maxsigcachesize=0 keeps nothing in either cache.
+
 Stratum server of the node (miner/stratum_server.py; needs -miningaddress, KawPow only):
 -stratumport=<port> (off without it), -stratumbind=<addr> (default 127.0.0.1), -stratumsharebits=<n>
 (share target 2^(256-n) - 1 as -minertargetbits; the effective target is the easier of it and the
